@@ -41,6 +41,10 @@ instrument samples instead of bracketing every launch), `per_rank` (kernel_ms an
 events around the SYRK kernel and around the collective on each rank's own stream), `n_ranks_seen` (fsnap_comm_info),
 `transport` (rccl | p2p: `--transport`) and, at N = 1, `cpu_baseline` (the oracle's restatement of the reference's numpy path timed on this
 box's host cores; a reported baseline, not the target).
+
+`--dump-outputs DIR` writes, after the timed region, what rank 0's last timed step returned as DIR/<name>.npy (float64):
+beta, rank, rcond_estimate and the statistics G, c, scalars it left in HBM.  The synthetic inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -97,7 +101,34 @@ def parse(argv=None):
                          "windows (one node; ranks may SHARE a device, which RCCL refuses -- how N > 1 runs on a one-GPU box)")
     ap.add_argument("--job-timeout", type=float, default=1800.0, help="launcher: seconds before a hung job is killed")
     ap.add_argument("--option", action="append", default=[], help="library option key=value (include/fsnap_hip.h: nblocks, nsplit, tiled, quad_min_rows, ...)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (beta, rank, rcond estimate and the "
+                         "statistics G, c, scalars behind the device pointer it hands back) as DIR/<name>.npy, float64")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_BYTES = 64_000_000    # --dump-outputs: the files together stay below this; a larger G is replaced by a fixed sample
+
+
+def dump_outputs(outdir, arrays):
+    """Write {name: array} as outdir/<name>.npy in float64.  When the whole set exceeds DUMP_MAX_BYTES, the largest array
+    is replaced by <name>_sample (entries at fixed, seeded flat positions) and <name>_sample_index (those positions)."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        big = max(arrays, key=lambda k: arrays[k].nbytes)
+        a = arrays.pop(big).ravel()
+        n = min(a.size, (DUMP_MAX_BYTES - (total - a.nbytes)) // 16)
+        idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+        arrays[f"{big}_sample"] = a[idx]
+        arrays[f"{big}_sample_index"] = idx.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -356,9 +387,10 @@ def run_mode(ctx, args, mode, rank, world, multi, _capi):
     info = ctx.launch_info()
 
     def step():
+        # (beta, rank, rcond estimate, device address of the statistics)
         if multi:
-            return ctx.fit_dist(_capi.SOLVE_RIDGE, ALPHA, Kc)[0]     # kernel -> in-place ncclAllReduce -> solve, every rank
-        return ctx.fit_resident(_capi.SOLVE_RIDGE, ALPHA)[0]         # the Solver classes' single-GPU path
+            return ctx.fit_dist(_capi.SOLVE_RIDGE, ALPHA, Kc)     # kernel -> in-place ncclAllReduce -> solve, every rank
+        return ctx.fit_resident(_capi.SOLVE_RIDGE, ALPHA)         # the Solver classes' single-GPU path
 
     def fence():
         if multi:
@@ -378,20 +410,26 @@ def run_mode(ctx, args, mode, rank, world, multi, _capi):
         sampled0 = ctx.timing_count()[0]
         ctx.set_option("timing_every", every)             # the next launch (timed step 0) is a sampled one
         t0 = time.perf_counter()
-        beta = None
+        res = None
         for _ in range(args.steps):
-            beta = step()
+            res = step()
         fence()
         elapsed = time.perf_counter() - t0
+        beta = res[0]
+        outputs = None
+        if args.dump_outputs and rank == 0:
+            # the statistics of the last timed step, still in the buffer whose address it returned
+            G, c, scal = ctx.download_packed(res[3], Kc)
+            outputs = {"beta": beta, "rank": [res[1]], "rcond_estimate": [res[2]], "G": G, "c": c, "scalars": scal}
         ctx.set_option("timing_every", 0)
         # kernel times of the timed steps: HIP events recorded on the kernel's stream, read now
         nh = min(ctx.timing_count()[0] - sampled0, 256)
         syrk_hist, red_hist = ctx.timing_history(nh)
         comm_hist = ctx.timing_history_comm(nh) if multi else np.full(nh, -1.0)
         comm_ms = float(np.mean(comm_hist[comm_hist >= 0])) if np.any(comm_hist >= 0) else 0.0
-        return elapsed, beta, float(np.mean(syrk_hist)), float(np.mean(red_hist)), comm_ms, nh
+        return elapsed, beta, float(np.mean(syrk_hist)), float(np.mean(red_hist)), comm_ms, nh, outputs
 
-    elapsed, beta, syrk_ms, red_ms, comm_ms, nh = timed()
+    elapsed, beta, syrk_ms, red_ms, comm_ms, nh, outputs = timed()
     # per-rank numbers, max-over-ranks wall time
     per_rank = np.zeros((world, 4))
     per_rank[rank] = (elapsed, syrk_ms, comm_ms, float(m))
@@ -402,6 +440,7 @@ def run_mode(ctx, args, mode, rank, world, multi, _capi):
         "kernel_ms": [float(x) for x in per_rank[:, 1]], "allreduce_ms": [float(x) for x in per_rank[:, 2]],
         "rows_per_rank": [int(x) for x in per_rank[:, 3]], "elapsed_per_rank_s": [float(x) for x in per_rank[:, 0]],
         "reduce_ms": red_ms, "sampled": nh, "info": info, "upload_ms": upload_ms, "upload_how": upload_how, "A": A, "b": b, "w": w,
+        "outputs": outputs,
     }
     return out
 
@@ -623,6 +662,7 @@ def run_rank(args):
             continue
         results[mode] = run_mode(ctx, args, mode, rank, world, multi, _capi)
     head = results[modes[0]]                               # what `value` reports
+    dumped = dump_outputs(args.dump_outputs, head["outputs"]) if head["outputs"] is not None else None
 
     pipelined = None
     if rank == 0 and world == 1 and not args.force_dist and args.pipelined:
@@ -742,6 +782,9 @@ def run_rank(args):
             out["pipelined"] = pipelined
         if svd_extra is not None:
             out["svd_solver"] = svd_extra
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "files": [f + ".npy" for f in dumped],
+                                   "of": f"the last of the {args.steps} timed steps ({head['mode']})"}
         if not args.no_cpu_baseline:
             if world == 1:
                 out["cpu_baseline"] = cpu_baseline(head["A"], head["b"], head["w"], head["beta"])

@@ -44,3 +44,34 @@ def test_traffic_is_null_for_any_other_shape_geometry_or_kernel():
         assert traffic is None and "recorded for" in why
     other = dict(info, chunks_per_wave=info["chunks_per_wave"] + 1)
     assert bench.recorded_traffic(rec["rows"], rec["K"], other, rec["kernel"])[0] is None
+
+
+def test_dump_outputs_writes_float64_files_within_the_size_limit(tmp_path):
+    import numpy as np
+
+    bench = _bench()
+    beta = np.arange(5.0)
+    paths = bench.dump_outputs(str(tmp_path / "small"), {"beta": beta, "rank": [5]})
+    assert paths == ["beta", "rank"]
+    got = np.load(tmp_path / "small" / "beta.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, beta)
+    # a set above the limit: the largest array becomes a fixed sample (the same positions on every run) plus its positions
+    G = np.random.default_rng(3).standard_normal((3000, 3000))
+    bench.DUMP_MAX_BYTES = 1_000_000
+    names = bench.dump_outputs(str(tmp_path / "big"), {"G": G, "c": beta})
+    assert names == ["G_sample", "G_sample_index", "c"]
+    total = sum(os.path.getsize(tmp_path / "big" / (n + ".npy")) for n in names)
+    assert total <= 1_000_000 + 3 * 128                               # (npy headers)
+    idx = np.load(tmp_path / "big" / "G_sample_index.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "big" / "G_sample.npy"), G.ravel()[idx])
+    bench.dump_outputs(str(tmp_path / "again"), {"G": G, "c": beta})
+    assert np.array_equal(np.load(tmp_path / "again" / "G_sample_index.npy"), idx)
+
+
+def test_steps_must_be_positive():
+    import pytest
+
+    bench = _bench()
+    assert bench.parse(["--steps", "7", "--warmup", "2"]).steps == 7
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])

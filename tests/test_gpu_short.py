@@ -156,21 +156,43 @@ def test_short_kernel_strided_rows_bound_in_place(ctx):
 
 def test_short_kernel_row_space_solve_of_an_ill_conditioned_short_system(ctx):
     # the row-space passes bring per-row pairs of their own (statistics of Q): kernel 1S on pairs from HBM inside fsnap_lstsq_rows
+    # The rows come from LAPACK / BLAS calls, whose last bits follow the host's BLAS thread count, and at kappa 1e9 those bits
+    # move the GPU's answer by ~1e-5 elementwise, as much as the bar: on one BLAS thread the rows are the same on every run.
+    from threadpoolctl import threadpool_limits
+
     m, K = 9000, 142
-    rng = np.random.default_rng(17)
-    U, _ = np.linalg.qr(rng.standard_normal((m, K)))
-    V, _ = np.linalg.qr(rng.standard_normal((K, K)))
-    sv = np.logspace(0, -9, K)
-    A = (U * sv) @ V.T
-    beta_star = rng.standard_normal(K)
-    b = A @ beta_star + 1e-6 * rng.standard_normal(m)
-    w = rng.uniform(0.5, 2.0, m)
+    with threadpool_limits(limits=1):
+        rng = np.random.default_rng(17)
+        U, _ = np.linalg.qr(rng.standard_normal((m, K)))
+        V, _ = np.linalg.qr(rng.standard_normal((K, K)))
+        sv = np.logspace(0, -9, K)
+        A = (U * sv) @ V.T
+        beta_star = rng.standard_normal(K)
+        b = A @ beta_star + 1e-6 * rng.standard_normal(m)
+        w = rng.uniform(0.5, 2.0, m)
     ctx.upload_rows(A, b)
     ctx.set_weights(w)
     beta, rank, info = ctx.lstsq_rows(1e-13)
     assert rank == K
-    ref = orc.svd_fit(A, b, w)
+    ref = exact_lstsq(A, b, w)
     assert maxrel(beta, ref) < max(1e-6, 50 * 1e9 * 2.2e-16)
+
+
+def exact_lstsq(A, b, w, steps=6):
+    """The weighted least-squares solution to ~1e-8 relative at kappa 1e9: the oracle's lstsq, then refinement of the normal
+    equations with residual and gradient in extended precision.  lstsq alone is only good to ~kappa eps per coefficient, and
+    which rounding it lands on follows the host's BLAS (thread count, CPU): two hosts' answers differ by ~1e-5, as much as
+    the bar of the test."""
+    import scipy.linalg
+
+    x = orc.svd_fit(A, b, w)
+    aw, bw = orc.weight_rows(A, b, w)
+    R = np.linalg.qr(aw, mode="r")
+    awl, bwl, xl = aw.astype(np.longdouble), bw.astype(np.longdouble), x.astype(np.longdouble)
+    for _ in range(steps):
+        g = np.asarray(awl.T @ (bwl - awl @ xl), dtype=np.float64)
+        xl = xl + scipy.linalg.solve_triangular(R, scipy.linalg.solve_triangular(R, g, trans="T"))
+    return np.asarray(xl, dtype=np.float64)
 
 
 def test_row_space_solve_at_the_ace_width_on_the_two_wave_pass_kernel(ctx):
