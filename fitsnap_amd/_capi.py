@@ -27,6 +27,8 @@ PROBE_OF = {SOLVE_LSTSQ: SOLVE_LSTSQ_PROBE, SOLVE_RIDGE: SOLVE_RIDGE_PROBE, SOLV
 BASE_OF = {v: k for k, v in PROBE_OF.items()}
 COMM_ID_BYTES = 128
 REDUCE_SUM, REDUCE_MAX, REDUCE_MIN = 0, 1, 2
+MERR_IID, MERR_ABC, MERR_FULL = 0, 1, 2
+MERR_METHODS = {"iid": MERR_IID, "abc": MERR_ABC, "full": MERR_FULL}
 
 _P_D = POINTER(c_double)
 _P_U8 = POINTER(c_uint8)
@@ -60,6 +62,8 @@ SIGNATURES = {
     "fsnap_weight_rows_device": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "fsnap_predict": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "fsnap_residual_rhs": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_double)]),
+    "fsnap_merr_eval": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_double, POINTER(c_double), c_void_p,
+                                c_void_p]),
     "fsnap_solve": (c_int, [c_int, c_double, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_double)]),
     "fsnap_cond_info": (c_int, [c_void_p]),
     "fsnap_lasso_gram": (c_int, [c_int64, c_void_p, c_void_p, c_double, c_double, c_int64, c_double, c_void_p,
@@ -570,6 +574,23 @@ class HipContext:
         sse = c_double(0.0)
         self._check(self._lib.fsnap_residual_rhs(self._h, _ptr(beta), _ptr(s), byref(sse) if want_sse else None))
         return s, (sse.value if want_sse else None)
+
+    def merr_eval(self, method, c, q, d):
+        """MERR log-posterior pass over the resident training rows (``fsnap_merr_eval``): returns (val, g, h) with
+        val = sum of the per-row terms (without the density's constants), g = dval/de x, h = dval/dv x o x summed over
+        the rows.  method: "iid" / "abc" / "full" or a MERR_* code; q = sigma^2, zero outside the embedded columns."""
+        code = MERR_METHODS.get(method, method) if isinstance(method, str) else int(method)
+        if isinstance(method, str) and method not in MERR_METHODS:
+            raise ValueError(f"unknown MERR method {method!r} (iid, abc or full)")
+        c = _f64(c, "c")
+        q = _f64(q, "q")
+        if c.shape != (self.K,) or q.shape != (self.K,):
+            raise ValueError(f"c / q have shapes {c.shape} / {q.shape}, expected ({self.K},)")
+        val = c_double(0.0)
+        g = np.empty(self.K)
+        h = np.empty(self.K)
+        self._check(self._lib.fsnap_merr_eval(self._h, code, self.K, _ptr(c), _ptr(q), float(d), byref(val), _ptr(g), _ptr(h)))
+        return val.value, g, h
 
     def normal_eq_accumulate(self, d_packed_ptr: int):
         """d_packed (device) += statistics of the resident rows (streaming / transpose-trick accumulation)."""

@@ -6,7 +6,8 @@ input is either a dict of dicts (library mode, input.py:141-151) or an INI file 
 with configparser (input.py:110-140).  Only keys the hot path needs are typed and
 defaulted here, with the reference's defaults:
 
-  [SOLVER] solver=SVD, compute_testerrs, detailed_errors   (solver_sections/solver.py:15-30)
+  [SOLVER] solver=SVD, compute_testerrs, detailed_errors, nsam, cov_nugget,
+           merr_mult=0, merr_method=abc, merr_cfs=all       (solver_sections/solver.py:15-35)
   [RIDGE]  alpha=1.0E-8, local_solver=0                     (solver_sections/ridge.py:13-14)
   [ARD]    alphabig, alphasmall, lambdabig, lambdasmall, threshold_lambda, directmethod,
            scap=1e-3, scai=1e-3, logcut=0.3                 (solver_sections/ard.py:13-21)
@@ -162,6 +163,9 @@ class Config:
             compute_testerrs=_get(sol, "compute_testerrs", "0", "bool"),
             detailed_errors=_get(sol, "detailed_errors", "0", "bool"),
             nsam=_get(sol, "nsam", "0", "int"), cov_nugget=_get(sol, "cov_nugget", "0.0", "float"),
+            # MERR (solver_sections/solver.py:33-35)
+            merr_mult=_get(sol, "merr_mult", "0", "bool"), merr_method=_get(sol, "merr_method", "abc", "str"),
+            merr_cfs=_get(sol, "merr_cfs", "all", "str"),
             true_multinode=1 if solver == "ScaLAPACK" else 0)
 
         def not_used(section):

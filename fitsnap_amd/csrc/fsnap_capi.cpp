@@ -1858,6 +1858,46 @@ int fsnap_residual_rhs(fsnap_ctx* ctx, const double* beta, double* s, double* ss
     return FSNAP_OK;
 }
 
+int fsnap_merr_eval(fsnap_ctx* ctx, int method, int64_t K, const double* c, const double* q, double d, double* val,
+                    double* g, double* h) {
+    if (!ctx) return FSNAP_E_ARG;
+    int rc;
+    if ((rc = check_rows(ctx)) || (rc = check_weights(ctx))) return rc;
+    if (!c || !q || !val || !g || !h) return ctx->fail(FSNAP_E_ARG, "fsnap_merr_eval: NULL argument");
+    if (K != ctx->K) return ctx->fail(FSNAP_E_ARG, "fsnap_merr_eval: K = %lld, the resident rows have %lld columns",
+                                      (long long)K, (long long)ctx->K);
+    if (method != FSNAP_MERR_IID && method != FSNAP_MERR_ABC && method != FSNAP_MERR_FULL)
+        return ctx->fail(FSNAP_E_ARG, "fsnap_merr_eval: unknown method %d", method);
+    if (K > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "fsnap_merr_eval: K = %lld too large", (long long)K);
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    const int nb = fsnap::merr_num_blocks(ctx->m, (int)K);
+    const bool two = K > fsnap::MERR_ONE_PASS_MAX_K;
+    const size_t nout = 2 * (size_t)K + 1;
+    if (!ctx->merr_cq.ensure(2 * (size_t)K * 8) || !ctx->merr_part.ensure((size_t)nb * nout * 8) ||
+        !ctx->merr_out.ensure(nout * 8) ||
+        (two && (!ctx->merr_u.ensure(2 * (size_t)ctx->m * 8) || !ctx->merr_vpart.ensure((size_t)nb * 8))))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(merr) failed");
+    const unsigned char* mask = ctx->dmask;
+    if (!mask) {
+        if ((rc = ensure_ones(ctx))) return rc;
+        mask = (const unsigned char*)ctx->ones.p;
+    }
+    double* dcq = (double*)ctx->merr_cq.p;
+    FSNAP_HIP(hipMemcpyAsync(dcq, c, (size_t)K * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(c)");
+    FSNAP_HIP(hipMemcpyAsync(dcq + K, q, (size_t)K * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(q)");
+    FSNAP_HIP(fsnap::launch_merr(ctx->dA, ctx->lda, dcq, ctx->m, (int)K, ctx->db, ctx->dw, mask,
+                                 method == FSNAP_MERR_ABC ? fsnap::MERR_ABC : fsnap::MERR_IID, d,
+                                 two ? (double*)ctx->merr_u.p : nullptr, two ? (double*)ctx->merr_vpart.p : nullptr,
+                                 (double*)ctx->merr_part.p, (double*)ctx->merr_out.p, ctx->stream),
+              "launch fsnap_merr_rows_k");
+    const double* out = (const double*)ctx->merr_out.p;
+    FSNAP_HIP(hipMemcpyAsync(g, out, (size_t)K * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(g)");
+    FSNAP_HIP(hipMemcpyAsync(h, out + K, (size_t)K * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(h)");
+    FSNAP_HIP(hipMemcpyAsync(val, out + 2 * K, 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(val)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    return FSNAP_OK;
+}
+
 int fsnap_timing(fsnap_ctx* ctx, double* ms, int n) {
     if (!ctx || !ms || n < 0 || n > 8) return FSNAP_E_ARG;
     FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");

@@ -103,6 +103,8 @@ struct fsnap_ctx {
     const double* wpack_override = nullptr;       // per-row pairs to use INSTEAD of wpack (row-space passes only)
     int64_t dcat_rows = -1;                       // number of rows the categories on the device belong to
     DevBuf du, dspart, dsvec;                     // refinement: row weights u, per-workgroup partials, s
+    DevBuf merr_cq, merr_part, merr_out;          // fsnap_merr_eval: [c | q], partials [g | h | val] per workgroup, sums
+    DevBuf merr_u, merr_vpart;                    // ... K > 288: per-row (alpha w, beta w^2), per-workgroup values
     double* pinned = nullptr;                     // page-locked host staging of the packed statistics: plain (coarse-grained)
                                                   // pinned memory, the target of DMA copies only -- copies into COHERENT
                                                   // host memory were bimodal (2 MB in 0.05 or in 8 ms)

@@ -141,6 +141,16 @@ hipError_t launch_error_stats(const double* truth, const double* pred, const dou
 hipError_t launch_gemvT_rows(const double* A, int64_t lda, const double* u, int64_t m, int K, double* partial,
                              double* out, hipStream_t st);
 
+// MERR log-posterior pass (fsnap_merr.hip).  method: MERR_IID / MERR_ABC (MERR_FULL is computed as MERR_IID);
+// cq[2K] = [c | q] on the device; out[2K + 1] = [g | h | val].  Scratch: partial[merr_num_blocks(m, K)][2K + 1]; for
+// K > MERR_ONE_PASS_MAX_K also u[2m] (per-row alpha w, beta w^2) and val_part[merr_num_blocks(m, K)]
+constexpr int MERR_IID = 0, MERR_ABC = 1, MERR_FULL = 2;
+constexpr int MERR_ONE_PASS_MAX_K = 288;
+int merr_num_blocks(int64_t m, int K);
+hipError_t launch_merr(const double* A, int64_t lda, const double* cq, int64_t m, int K, const double* b, const double* w,
+                       const unsigned char* mask, int method, double d, double* u, double* val_part, double* partial,
+                       double* out, hipStream_t st);
+
 // Row-space solve (fsnap_trsm.hip).  Q <- X R^-1 by blocked substitution over the columns, one wave per 64 rows:
 // first pass X = diag(w_eff) A (src = A, leading dimension lds, per-row pairs wpack = (w_eff, w_eff b); rows with
 // w_eff = 0 become zero rows), later passes X = Q in place (src = Q, wpack = nullptr).  R: device, K16 x K16 row-major

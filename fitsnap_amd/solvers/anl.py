@@ -23,33 +23,10 @@ class ANL(Solver):
         nbas = len(c)
         npt = float(s[2])
         cov_nugget = config.sections["SOLVER"].cov_nugget
-        transposed = False
-        if config.sections["EXTRAS"].apply_transpose:
-            # anl.py:31-36: the regression is run on (aw.T aw, aw.T bw) = (G, c) instead of the rows when
-            # cond(aw)^2 = lambda_max(G) / lambda_min(G) < 1 / eps -- all of it K x K host algebra on the statistics
-            with blas_threads(len(c)):
-                ev = np.linalg.eigvalsh(G)
-            if abs(ev[-1]) / max(abs(ev[0]), np.finfo(float).tiny) < 1.0 / np.finfo(float).eps:
-                transposed = True
-            else:
-                print("The Matrix is ill-conditioned for the transpose trick")
+        transposed = config.sections["EXTRAS"].apply_transpose and transpose_trick_ok(G)
+        invptp, fit, sse = posterior_noise(pt, G, c, cov_nugget, transposed)
         if transposed:
-            with blas_threads(nbas):
-                invptp = np.linalg.pinv(G.T @ G + cov_nugget * np.diag(np.ones((nbas,))))
-            invptp = invptp * 0.5 + invptp.T * 0.5
-            fit = np.dot(invptp, G.T @ c)
-            res = c - G @ fit
-            sse = float(res @ res)
             npt = float(nbas)                       # the "rows" of the transposed system
-        else:
-            with blas_threads(nbas):            # (an SVD of K x K: _hostblas.py)
-                invptp = np.linalg.pinv(G + cov_nugget * np.diag(np.ones((nbas,))))       # anl.py:39
-            invptp = invptp * 0.5 + invptp.T * 0.5                                     # anl.py:40
-            fit = np.dot(invptp, c)
-            # res = bw - aw @ fit; bp = res.res / 2  (anl.py:46-47): exact streamed residual on the GPU
-            ctx = pt.hip()
-            _, sse = ctx.predict(fit, want_preds=False, want_sse=True)
-            sse = pt.allreduce_scalar(sse)
         bp = sse / 2.0
         ap = (npt - nbas) / 2.0
         sigmahat = bp / (ap - 1.0)
@@ -63,3 +40,45 @@ class ANL(Solver):
         nsam = config.sections["SOLVER"].nsam
         if nsam:
             self.fit_sam = np.random.multivariate_normal(self.fit, self.cov, size=(nsam,))   # anl.py:63-65
+
+
+def transpose_trick_ok(G):
+    """anl.py:31-36 / merr.py:19-24: the regression may run on (aw.T aw, aw.T bw) = (G, c) instead of the rows when
+    cond(aw)^2 = lambda_max(G) / lambda_min(G) < 1 / eps -- K x K host algebra on the statistics."""
+    with blas_threads(G.shape[0]):
+        ev = np.linalg.eigvalsh(G)
+    if abs(ev[-1]) / max(abs(ev[0]), np.finfo(float).tiny) < 1.0 / np.finfo(float).eps:
+        return True
+    print("The Matrix is ill-conditioned for the transpose trick")
+    return False
+
+
+def posterior_noise(pt, G, c, cov_nugget, transposed, keep=None):
+    """The analytical posterior of ANL (anl.py:38-50, merr.py:39-50): ``invptp = pinv(P + nugget I)`` symmetrised, the
+    mean ``fit`` and the weighted residual sum of squares ``sse`` of the regression on the columns ``keep`` (a boolean
+    mask; None = all).  P = G[keep, keep] on the rows, whose exact residual is one streamed pass over them on the GPU
+    (``fsnap_predict``, summed over the ranks); with ``transposed`` the "rows" are (G[:, keep], c), all host algebra.
+    Returns (invptp, fit over the kept columns, sse)."""
+    if transposed:
+        Gc = G if keep is None else G[:, keep]
+        nbas = Gc.shape[1]
+        with blas_threads(nbas):
+            invptp = np.linalg.pinv(Gc.T @ Gc + cov_nugget * np.diag(np.ones((nbas,))))
+        invptp = invptp * 0.5 + invptp.T * 0.5
+        fit = np.dot(invptp, Gc.T @ c)
+        res = c - Gc @ fit
+        return invptp, fit, float(res @ res)
+    Gk = G if keep is None else G[np.ix_(keep, keep)]
+    ck = c if keep is None else c[keep]
+    nbas = len(ck)
+    with blas_threads(nbas):            # (an SVD of K x K: _hostblas.py)
+        invptp = np.linalg.pinv(Gk + cov_nugget * np.diag(np.ones((nbas,))))       # anl.py:39
+    invptp = invptp * 0.5 + invptp.T * 0.5                                        # anl.py:40
+    fit = np.dot(invptp, ck)
+    full = fit
+    if keep is not None:
+        full = np.zeros(len(c))
+        full[keep] = fit
+    # res = bw - aw @ fit; bp = res.res / 2  (anl.py:46-47): exact streamed residual on the GPU
+    _, sse = pt.hip().predict(full, want_preds=False, want_sse=True)
+    return invptp, fit, pt.allreduce_scalar(sse)

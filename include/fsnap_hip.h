@@ -260,6 +260,20 @@ int fsnap_predict(fsnap_ctx* ctx, const double* beta, double* preds, double* sse
  * beta, s: host; *sse (optional) receives sum (w (b - A beta))^2. */
 int fsnap_residual_rhs(fsnap_ctx* ctx, const double* beta, double* s, double* sse);
 
+/* Model-error (MERR) log-posterior of the resident training rows and its exact gradient, one pass over A
+ * (fitsnap3lib/solvers/lreg.py logpost_emb; kernel M1, or kernels M2 + M3 above 288 columns).  With x_i = w_i a_i,
+ * e_i = x_i . c - w_i b_i and v_i = sum_j x_ij^2 q_j + d over the rows of the current mask (weight zero included):
+ *   *val = sum_i l(e_i, v_i),  g[K] = sum_i dl/de x_i,  h[K] = sum_i dl/dv x_i o x_i
+ * with  iid / full: l = -e^2 / (2 v) - log(v) / 2;  abc: l = -(|e| - sqrt(v))^2 / (2 0.01).  The constants of the density
+ * (-n log(2 pi) / 2, or -log(2 pi) / 2 - log(0.1) once for abc) are the caller's, so that the sums of several ranks add.
+ * method: FSNAP_MERR_*; K must equal the resident rows' width; c, q (q_j = sigma_j^2, 0 outside the embedded columns):
+ * host in; val, g, h: host out.  The workspace stays on the context.  Bit-identical run to run. */
+#define FSNAP_MERR_IID 0
+#define FSNAP_MERR_ABC 1
+#define FSNAP_MERR_FULL 2
+int fsnap_merr_eval(fsnap_ctx* ctx, int method, int64_t K, const double* c, const double* q, double d, double* val,
+                    double* g, double* h);
+
 /* ---- K x K solve (host side, no context needed) ----------------------------------- */
 
 /* Solve the K x K system given the statistics.  `kind` is one of FSNAP_SOLVE_*;
