@@ -28,6 +28,7 @@ BASE_OF = {v: k for k, v in PROBE_OF.items()}
 COMM_ID_BYTES = 128
 REDUCE_SUM, REDUCE_MAX, REDUCE_MIN = 0, 1, 2
 MERR_IID, MERR_ABC, MERR_FULL = 0, 1, 2
+CAND_ERROR_SUMS, CAND_RHS = 0, 1            # fsnap_candidate_rows: what
 MERR_METHODS = {"iid": MERR_IID, "abc": MERR_ABC, "full": MERR_FULL}
 
 _P_D = POINTER(c_double)
@@ -104,6 +105,14 @@ SIGNATURES = {
     "fsnap_timing_history_comm": (c_int, [c_void_p, c_void_p, c_int]),
     "fsnap_rowspace_chain": (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_double, c_void_p, POINTER(c_int), c_void_p]),
     "fsnap_launch_info": (c_int, [c_void_p, POINTER(c_int64), c_int]),
+    "fsnap_cat_chunks": (c_int, [c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int64)]),
+    "fsnap_cat_info": (c_int, [c_void_p, POINTER(c_int64), c_int]),
+    "fsnap_cat_prepare": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_int64)]),
+    "fsnap_cat_normal_eq": (c_int, [c_void_p, c_int64, POINTER(c_void_p)]),
+    "fsnap_cat_normal_eq_dist": (c_int, [c_void_p, POINTER(c_int64), c_int64, c_int, POINTER(c_void_p)]),
+    "fsnap_fit_candidates": (c_int, [c_void_p, c_int64, c_int, c_double, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p,
+                                     c_void_p, POINTER(c_void_p)]),
+    "fsnap_candidate_rows": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p]),
 }
 
 _lib = None
@@ -298,6 +307,40 @@ def make_dense_pinv():
 
 
 TRANSPORTS = ("none", "rccl", "p2p")
+
+
+def _cat_info(lib, handle):
+    info = (c_int64 * 5)()
+    rc = lib.fsnap_cat_info(handle, info, 5)
+    if rc != OK:
+        raise_status(rc, "fsnap_cat_info failed")
+    return {"layout": info[0], "ncat": info[1], "K": info[2], "chunk_rows": info[3], "max_p": info[4]}
+
+
+def cat_limits():
+    """The candidate kernels' fixed sizes as the library has them: {"chunk_rows": rows per chunk, "max_p": candidates per
+    launch of the row kernel}."""
+    info = _cat_info(load_library(), None)
+    return {"chunk_rows": info["chunk_rows"], "max_p": info["max_p"]}
+
+
+def cat_chunks(cat, ncat: int, mask=None):
+    """Host half of the candidate kernels' work layout (``fsnap_cat_chunks``): (sorted row ids, (n, 3) chunks of
+    (category, first position, rows))."""
+    lib = load_library()
+    cat = np.ascontiguousarray(cat, dtype=np.int32)
+    m = cat.shape[0]
+    mk = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+    if mk is not None and mk.shape != (m,):
+        raise ValueError("mask must have one entry per row")
+    idx = np.empty(max(m, 1), dtype=np.int32)
+    ch = np.empty((m + int(ncat), 3), dtype=np.int64)
+    n = c_int64(0)
+    rc = lib.fsnap_cat_chunks(m, _ptr(cat), _ptr(mk), int(ncat), _ptr(idx), _ptr(ch), byref(n))
+    if rc != OK:
+        raise_status(rc, (lib.fsnap_last_error(None) or b"").decode())
+    nrows = int(ch[:n.value, 2].sum())
+    return idx[:nrows].copy(), ch[:n.value].copy()
 
 
 def comm_id(transport: str = None) -> bytes:
@@ -641,6 +684,66 @@ class HipContext:
         if rc != OK:
             raise_status(rc, (self._lib.fsnap_last_error(self._h) or b"").decode() if rc < 0 else "")
         return beta, rank.value, rce.value
+
+    # -- batched candidate fits (fsnap_cat_prepare ... fsnap_candidate_rows) ------------------------------------------
+    def cat_prepare(self, cat, ncat: int) -> int:
+        """Category layout of the resident rows, mask and weights (the weights become the base weights w0); returns the
+        layout's tag, which every later call of the group names."""
+        cat = np.ascontiguousarray(cat, dtype=np.int32)
+        if cat.shape != (self.m,):
+            raise ValueError("cat must have one entry per row")
+        tag = c_int64(0)
+        self._check(self._lib.fsnap_cat_prepare(self._h, _ptr(cat), int(ncat), byref(tag)))
+        return tag.value
+
+    def cat_info(self):
+        """{"layout", "ncat", "K", "chunk_rows", "max_p"}: the layout the context holds now (fsnap_cat_info)."""
+        return _cat_info(self._lib, self._h)
+
+    def cat_normal_eq(self, layout: int) -> int:
+        """Per-category statistics of the training rows; returns the device address of the ncat packed blocks."""
+        ptr = c_void_p(None)
+        self._check(self._lib.fsnap_cat_normal_eq(self._h, int(layout), byref(ptr)))
+        return ptr.value
+
+    def cat_normal_eq_dist(self, layout: int, K: int, ncat: int):
+        """Collective form: the per-category statistics summed over the ranks, on every rank.  layout = 0 on a rank without
+        rows.  Returns (layout tag, device address)."""
+        ptr = c_void_p(None)
+        tag = c_int64(int(layout))
+        self._check(self._lib.fsnap_cat_normal_eq_dist(self._h, byref(tag), int(K), int(ncat), byref(ptr)))
+        return tag.value, ptr.value
+
+    def fit_candidates(self, layout: int, kind: int, param: float, S, K: int):
+        """Combination + K x K solve of every candidate: (beta (P, K), rank (P,), rcond (P,), device address of the P
+        packed buffers)."""
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        if S.ndim != 2:
+            raise ValueError("S must be (P, ncat)")
+        P, ncat = S.shape
+        beta = np.empty((P, int(K)))
+        rank = np.empty(P, dtype=np.int32)
+        rce = np.empty(P)
+        ptr = c_void_p(None)
+        rc = self._lib.fsnap_fit_candidates(self._h, int(layout), int(kind), float(param), _ptr(S), int(P), int(ncat), int(K),
+                                            _ptr(beta), _ptr(rank), _ptr(rce), byref(ptr))
+        if rc != OK:
+            raise_status(rc, (self._lib.fsnap_last_error(self._h) or b"").decode() if rc < 0 else "")
+        return beta, rank, rce, ptr.value
+
+    def candidate_rows(self, layout: int, beta, S, what: int, ncat: int):
+        """One pass over the rows for P coefficient vectors: (P, ncat, 4) error sums or (P, K) right-hand sides."""
+        beta = np.ascontiguousarray(beta, dtype=np.float64)
+        if beta.ndim != 2 or beta.shape[1] != self.K:
+            raise ValueError(f"beta must have shape (P, {self.K})")
+        P = beta.shape[0]
+        Sa = None if S is None else np.ascontiguousarray(S, dtype=np.float64)
+        if Sa is not None and Sa.shape != (P, int(ncat)):
+            raise ValueError(f"S must have shape ({P}, {int(ncat)})")
+        out = np.empty((P, int(ncat), 4) if what == CAND_ERROR_SUMS else (P, self.K))
+        self._check(self._lib.fsnap_candidate_rows(self._h, int(layout), _ptr(beta), _ptr(Sa), int(P), int(ncat), self.K,
+                                                   int(what), _ptr(out)))
+        return out
 
     # -- row-space least squares --------------------------------------------------------
     def lstsq_rows(self, rcond: float, K: int = None):

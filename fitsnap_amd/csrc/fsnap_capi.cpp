@@ -385,6 +385,13 @@ int staged_rows_h2d(fsnap_ctx* ctx, void* dst, const void* src, size_t rows, siz
     return FSNAP_OK;
 }
 
+// the category layout of the candidate kernels belongs to the rows it was prepared for: any change of the resident rows drops it
+void cand_forget(fsnap_ctx* ctx) {
+    ctx->cand_layout = 0;
+    ctx->cand_dA = nullptr;
+    ctx->cand_stats_K = 0;
+}
+
 int check_rows(fsnap_ctx* ctx) {
     if (!ctx->dA || !ctx->db || ctx->m <= 0) return ctx->fail(FSNAP_E_STATE, "no rows: call fsnap_upload_rows/fsnap_bind_rows first");
     return FSNAP_OK;
@@ -967,6 +974,7 @@ int fsnap_upload_rows(fsnap_ctx* ctx, const double* A, int64_t m, int64_t K, int
     ctx->m = m;
     ctx->K = K;
     ctx->lda = K;
+    cand_forget(ctx);
     return FSNAP_OK;
 }
 
@@ -979,6 +987,7 @@ int fsnap_drop_rows(fsnap_ctx* ctx) {
     ctx->dw = nullptr;
     ctx->dmask = nullptr;
     ctx->m = 0;
+    cand_forget(ctx);
     ctx->ntrain_resident = -1;
     ctx->wpack_valid = false;
     ctx->mirror_of = nullptr;
@@ -1005,6 +1014,7 @@ int fsnap_bind_rows(fsnap_ctx* ctx, const double* dA, int64_t m, int64_t K, int6
     ctx->m = m;
     ctx->K = K;
     ctx->lda = lda;
+    cand_forget(ctx);
     return FSNAP_OK;
 }
 
@@ -1029,6 +1039,7 @@ int fsnap_rows_alloc(fsnap_ctx* ctx, int64_t m, int64_t K) {
     ctx->m = m;
     ctx->K = K;
     ctx->lda = K;
+    cand_forget(ctx);
     return FSNAP_OK;
 }
 
@@ -1114,6 +1125,7 @@ int fsnap_assemble(fsnap_ctx* ctx, const double* raw, int64_t raw_rows, int64_t 
         return rc;
     hipStream_t st = ctx->stream;
     ctx->wpack_valid = false;      // the kernel below writes b and w of these rows
+    cand_forget(ctx);
     FSNAP_HIP(fsnap::launch_assemble(pd.raw, raw_ld, nrows, pd.src_row, pd.kind, pd.frac, pd.d, pd.truth, pd.weight,
                                      pd.fractions, pd.blank2J, ntypes, ncoeff, offcol,
                                      (double*)ctx->ownA.p + row0 * ctx->lda, ctx->lda, (double*)ctx->ownb.p + row0,
@@ -1987,6 +1999,284 @@ int fsnap_launch_info(fsnap_ctx* ctx, int64_t* info, int n) {
         out[7] = g.fused_pack ? 1 : 0;  // kernel id: 1 = wave-triangle, 2 = LDS-shared, 3 = one-wave triangle (1A), 4 = wave-triangle on packed weights (1P), 5 = triangle dealt to the four waves of a workgroup (1Q; chunks per WORKGROUP)
     }
     for (int i = 0; i < n; ++i) info[i] = out[i];
+    return FSNAP_OK;
+}
+
+}  // extern "C"
+
+// ---- batched candidate fits ------------------------------------------------------------------------------------
+
+namespace {
+
+int cand_check_layout(fsnap_ctx* ctx, int64_t layout, const char* who) {
+    if (!ctx->cand_dA || ctx->cand_dA != ctx->dA || ctx->cand_m != ctx->m || layout <= 0 || layout != ctx->cand_layout)
+        return ctx->fail(FSNAP_E_STATE, "%s: layout %lld is not the one the context holds (%lld): fsnap_cat_prepare again", who,
+                         (long long)layout, (long long)ctx->cand_layout);
+    return FSNAP_OK;
+}
+
+std::atomic<int64_t> cand_layout_counter{0};   // layout tags are unique over all contexts of the process
+
+bool cand_fits(int64_t n, int64_t K) {
+    return n > 0 && K > 0 && (double)n * (double)FSNAP_PACKED_LEN(K) * 8.0 <= (double)FSNAP_CAT_STATS_MAX_BYTES;
+}
+
+// kernels C1 + C1R into ctx->cand_stats (the rows must be prepared)
+int cand_stats_launch(fsnap_ctx* ctx) {
+    const int K = (int)ctx->K, ncat = ctx->cand_ncat;
+    const int64_t T = FSNAP_PACKED_LEN(K), nch = ctx->cand_nch_t;
+    const int64_t per = fsnap::cat_partial_doubles(K), NT = (K + 15) / 16, NP = NT * (NT + 1) / 2;
+    if (!ctx->cand_stats.ensure((size_t)ncat * T * 8) || !ctx->cand_part.ensure((size_t)(nch > 0 ? nch : 1) * per * 8))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(category statistics) failed");
+    double* part = (double*)ctx->cand_part.p;
+    double* cpart = part + nch * NP * 256;
+    double* spart = cpart + nch * NT * 16;
+    FSNAP_HIP(fsnap::launch_cat_syrk(ctx->dA, ctx->lda, ctx->db, (const double*)ctx->cand_w0.p, (const int*)ctx->cand_idx_t.p,
+                                     (const fsnap::CatChunk*)ctx->cand_ch_t.p, nch, K, part, cpart, spart, ctx->stream),
+              "launch fsnap_cat_syrk_k");
+    FSNAP_HIP(fsnap::launch_cat_reduce(part, cpart, spart, (const int*)ctx->cand_cb_t.p, ncat, K, (double*)ctx->cand_stats.p,
+                                       ctx->stream),
+              "launch fsnap_cat_reduce_k");
+    ctx->cand_stats_K = K;
+    return FSNAP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fsnap_cat_chunks(int64_t m, const int32_t* cat, const uint8_t* mask, int ncat, int32_t* idx, int64_t* chunks,
+                     int64_t* nchunks) {
+    if (m < 0 || m > 0x7FFFFFFF || (m > 0 && !cat) || ncat <= 0 || !idx || !chunks || !nchunks) {
+        fsnap::library_error() = "fsnap_cat_chunks: bad argument";
+        return FSNAP_E_ARG;
+    }
+    std::vector<int64_t> start((size_t)ncat + 1, 0);
+    for (int64_t i = 0; i < m; ++i) {
+        if (cat[i] >= ncat) {
+            char buf[160];
+            snprintf(buf, sizeof buf, "fsnap_cat_chunks: category %d of row %lld is not below %d", cat[i], (long long)i, ncat);
+            fsnap::library_error() = buf;
+            return FSNAP_E_ARG;
+        }
+        if (cat[i] >= 0 && (!mask || mask[i])) ++start[(size_t)cat[i] + 1];
+    }
+    for (int c = 0; c < ncat; ++c) start[(size_t)c + 1] += start[(size_t)c];
+    std::vector<int64_t> pos(start.begin(), start.end() - 1);
+    for (int64_t i = 0; i < m; ++i)
+        if (cat[i] >= 0 && (!mask || mask[i])) idx[pos[(size_t)cat[i]]++] = (int32_t)i;
+    int64_t n = 0;
+    for (int c = 0; c < ncat; ++c)
+        for (int64_t f = start[(size_t)c]; f < start[(size_t)c + 1]; f += fsnap::CAT_CHUNK_ROWS) {
+            chunks[3 * n] = c;
+            chunks[3 * n + 1] = f;
+            chunks[3 * n + 2] = std::min<int64_t>(fsnap::CAT_CHUNK_ROWS, start[(size_t)c + 1] - f);
+            ++n;
+        }
+    *nchunks = n;
+    return FSNAP_OK;
+}
+
+int fsnap_cat_info(const fsnap_ctx* ctx, int64_t* info, int n) {
+    if (!info || n < 0 || n > 5) return FSNAP_E_ARG;
+    const int64_t out[5] = {ctx ? ctx->cand_layout : 0, ctx && ctx->cand_layout ? ctx->cand_ncat : 0,
+                            ctx && ctx->cand_layout ? ctx->cand_stats_K : 0, fsnap::CAT_CHUNK_ROWS, fsnap::CAND_ROWS_MAX_P};
+    for (int i = 0; i < n; ++i) info[i] = out[i];
+    return FSNAP_OK;
+}
+
+int fsnap_cat_prepare(fsnap_ctx* ctx, const int32_t* cat, int ncat, int64_t* layout) {
+    if (!ctx) return FSNAP_E_ARG;
+    int rc;
+    cand_forget(ctx);                 // a prepare that fails leaves no layout behind
+    if ((rc = check_rows(ctx)) || (rc = check_weights(ctx))) return rc;
+    if (!cat || ncat <= 0 || !layout) return ctx->fail(FSNAP_E_ARG, "fsnap_cat_prepare: bad argument");
+    if (ctx->m > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "fsnap_cat_prepare: more than 2^31 - 1 rows");
+    if (!cand_fits(ncat, ctx->K))
+        return ctx->fail(FSNAP_E_ARG, "fsnap_cat_prepare: %d categories x %lld doubles exceed FSNAP_CAT_STATS_MAX_BYTES", ncat,
+                         (long long)FSNAP_PACKED_LEN(ctx->K));
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    const int64_t m = ctx->m;
+    std::vector<unsigned char> mask;
+    if (ctx->dmask) {
+        mask.resize((size_t)m);
+        FSNAP_HIP(hipMemcpyAsync(mask.data(), ctx->dmask, (size_t)m, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(mask)");
+        FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    }
+    // stable counting sort of the row ids by category, once over the training rows and once over all rows
+    std::vector<int32_t> idx_t((size_t)m + 1), idx_a((size_t)m + 1);
+    std::vector<int64_t> raw_t(3 * ((size_t)m + ncat)), raw_a(3 * ((size_t)m + ncat));
+    int64_t n_t = 0, n_a = 0;
+    if ((rc = fsnap_cat_chunks(m, cat, mask.empty() ? nullptr : mask.data(), ncat, idx_t.data(), raw_t.data(), &n_t)) ||
+        (rc = fsnap_cat_chunks(m, cat, nullptr, ncat, idx_a.data(), raw_a.data(), &n_a)))
+        return ctx->fail(rc, "%s", fsnap::library_error().c_str());
+    std::vector<fsnap::CatChunk> ch_t, ch_a;
+    std::vector<int32_t> cb_t((size_t)ncat + 1, 0), cb_a((size_t)ncat + 1, 0);
+    auto to_chunks = [&](const std::vector<int64_t>& raw, int64_t n, std::vector<fsnap::CatChunk>& ch, std::vector<int32_t>& cb) {
+        for (int64_t i = 0; i < n; ++i) ch.push_back(fsnap::CatChunk{raw[3 * i + 1], (int32_t)raw[3 * i], (int32_t)raw[3 * i + 2]});
+        // cbeg[c] = first chunk of category c (chunks are in category order)
+        int64_t j = 0;
+        for (int c = 0; c <= ncat; ++c) {
+            while (j < n && raw[3 * j] < c) ++j;
+            cb[(size_t)c] = (int32_t)j;
+        }
+    };
+    to_chunks(raw_t, n_t, ch_t, cb_t);
+    to_chunks(raw_a, n_a, ch_a, cb_a);
+    const size_t csz = sizeof(fsnap::CatChunk);
+    if (!ctx->cand_idx_t.ensure(idx_t.size() * 4) || !ctx->cand_idx_a.ensure(idx_a.size() * 4) ||
+        !ctx->cand_ch_t.ensure((ch_t.size() + 1) * csz) || !ctx->cand_ch_a.ensure((ch_a.size() + 1) * csz) ||
+        !ctx->cand_cb_t.ensure(cb_t.size() * 4) || !ctx->cand_cb_a.ensure(cb_a.size() * 4) || !ctx->cand_w0.ensure((size_t)m * 8))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(category layout) failed");
+    FSNAP_HIP(hipMemcpyAsync(ctx->cand_idx_t.p, idx_t.data(), idx_t.size() * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(index)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->cand_idx_a.p, idx_a.data(), idx_a.size() * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(index)");
+    if (!ch_t.empty())
+        FSNAP_HIP(hipMemcpyAsync(ctx->cand_ch_t.p, ch_t.data(), ch_t.size() * csz, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(chunks)");
+    if (!ch_a.empty())
+        FSNAP_HIP(hipMemcpyAsync(ctx->cand_ch_a.p, ch_a.data(), ch_a.size() * csz, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(chunks)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->cand_cb_t.p, cb_t.data(), cb_t.size() * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(chunks)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->cand_cb_a.p, cb_a.data(), cb_a.size() * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(chunks)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->cand_w0.p, ctx->dw, (size_t)m * 8, hipMemcpyDeviceToDevice, ctx->stream), "hipMemcpy(w0)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    ctx->cand_dA = ctx->dA;
+    ctx->cand_m = m;
+    ctx->cand_nch_t = (int64_t)ch_t.size();
+    ctx->cand_nch_a = (int64_t)ch_a.size();
+    ctx->cand_ncat = ncat;
+    ctx->cand_stats_K = 0;
+    ctx->cand_layout = ++cand_layout_counter;
+    *layout = ctx->cand_layout;
+    return FSNAP_OK;
+}
+
+int fsnap_cat_normal_eq(fsnap_ctx* ctx, int64_t layout, double** d_stats) {
+    if (!ctx) return FSNAP_E_ARG;
+    int rc;
+    if (!d_stats) return ctx->fail(FSNAP_E_ARG, "fsnap_cat_normal_eq: d_stats is NULL");
+    if ((rc = check_rows(ctx)) || (rc = cand_check_layout(ctx, layout, "fsnap_cat_normal_eq"))) return rc;
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    if ((rc = cand_stats_launch(ctx))) return rc;
+    *d_stats = (double*)ctx->cand_stats.p;
+    return FSNAP_OK;
+}
+
+int fsnap_cat_normal_eq_dist(fsnap_ctx* ctx, int64_t* layout, int64_t K, int ncat, double** d_stats) {
+    if (!ctx) return FSNAP_E_ARG;
+    if (!layout || !d_stats || !cand_fits(ncat, K)) return ctx->fail(FSNAP_E_ARG, "fsnap_cat_normal_eq_dist: bad argument");
+    if (!ctx->comm) return ctx->fail(FSNAP_E_STATE, "fsnap_cat_normal_eq_dist: no communicator (fsnap_comm_init first)");
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    const int64_t n = (int64_t)ncat * FSNAP_PACKED_LEN(K);
+    // as in fsnap_fit_dist: a rank that fails alone still takes part in the collective, with NaN statistics
+    if (!ctx->cand_stats.ensure((size_t)n * 8)) return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(category statistics) failed");
+    double* dp = (double*)ctx->cand_stats.p;
+    const bool have_rows = *layout != 0;
+    int local_rc = FSNAP_OK;
+    std::string local_err;
+    if (have_rows && cand_check_layout(ctx, *layout, "fsnap_cat_normal_eq_dist")) {
+        local_rc = FSNAP_E_STATE;
+    } else if (have_rows && (ctx->K != K || ctx->cand_ncat != ncat)) {
+        local_rc = ctx->fail(FSNAP_E_ARG, "fsnap_cat_normal_eq_dist: K = %lld, ncat = %d but the prepared rows have %lld, %d",
+                             (long long)K, ncat, (long long)ctx->K, ctx->cand_ncat);
+    } else if (have_rows) {
+        local_rc = cand_stats_launch(ctx);
+    } else if (hipMemsetAsync(dp, 0, (size_t)n * 8, ctx->stream) != hipSuccess) {
+        local_rc = ctx->fail(FSNAP_E_HIP, "hipMemsetAsync(category statistics) failed");
+    }
+    if (local_rc != FSNAP_OK) {
+        local_err = ctx->err;
+        (void)hipMemsetAsync(dp, 0xFF, (size_t)n * 8, ctx->stream);
+    }
+    int rc = fsnap_allreduce_device(ctx, dp, n);
+    if (local_rc != FSNAP_OK) return ctx->fail(local_rc, "%s", local_err.c_str());
+    if (rc) return rc;
+    if (!have_rows) {                 // a rank without rows: a layout of statistics only (no row pass can use it)
+        cand_forget(ctx);
+        ctx->cand_layout = ++cand_layout_counter;
+        *layout = ctx->cand_layout;
+    }
+    ctx->cand_ncat = ncat;
+    ctx->cand_stats_K = K;
+    *d_stats = dp;
+    return FSNAP_OK;
+}
+
+int fsnap_fit_candidates(fsnap_ctx* ctx, int64_t layout, int kind, double param, const double* S, int P, int ncat, int64_t K,
+                         double* beta, int* rank, double* rcond_est, double** d_packed) {
+    if (!ctx) return FSNAP_E_ARG;
+    if (!S || P <= 0 || !beta || !rank || !rcond_est) return ctx->fail(FSNAP_E_ARG, "fsnap_fit_candidates: bad argument");
+    if (layout <= 0 || layout != ctx->cand_layout || ctx->cand_stats_K <= 0 || !ctx->cand_stats.p)
+        return ctx->fail(FSNAP_E_STATE, "fsnap_fit_candidates: no per-category statistics of layout %lld on the context "
+                                        "(fsnap_cat_prepare + fsnap_cat_normal_eq first)", (long long)layout);
+    if (ncat != ctx->cand_ncat || K != ctx->cand_stats_K)
+        return ctx->fail(FSNAP_E_ARG, "fsnap_fit_candidates: ncat = %d, K = %lld but the statistics have %d, %lld", ncat,
+                         (long long)K, ctx->cand_ncat, (long long)ctx->cand_stats_K);
+    if (!cand_fits(P, K))
+        return ctx->fail(FSNAP_E_ARG, "fsnap_fit_candidates: %d candidates x %lld doubles exceed FSNAP_CAT_STATS_MAX_BYTES", P,
+                         (long long)FSNAP_PACKED_LEN(K));
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    const int64_t T = FSNAP_PACKED_LEN(K);
+    if (!ctx->cand_S.ensure((size_t)P * ncat * 8) || !ctx->cand_out.ensure((size_t)P * T * 8))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(candidate statistics) failed");
+    FSNAP_HIP(hipMemcpyAsync(ctx->cand_S.p, S, (size_t)P * ncat * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(S)");
+    double* out = (double*)ctx->cand_out.p;
+    FSNAP_HIP(fsnap::launch_cand_combine((const double*)ctx->cand_stats.p, (const double*)ctx->cand_S.p, P, ncat, (int)K, out,
+                                         ctx->stream),
+              "launch fsnap_cand_combine_k");
+    if (ctx->mirror_of == out) ctx->mirror_of = nullptr;     // the buffer was rewritten
+    ctx->chol_factor_of = nullptr;
+    for (int p = 0; p < P; ++p) {
+        int rc = fsnap_solve_device_rhs(ctx, kind, param, K, out + (int64_t)p * T, nullptr, beta + (int64_t)p * K, rank + p,
+                                        rcond_est + p);
+        if (rc) return rc;
+    }
+    if (d_packed) *d_packed = out;
+    return FSNAP_OK;
+}
+
+int fsnap_candidate_rows(fsnap_ctx* ctx, int64_t layout, const double* beta, const double* S, int P, int ncat, int64_t K_,
+                         int what, double* out) {
+    if (!ctx) return FSNAP_E_ARG;
+    int rc;
+    if ((rc = check_rows(ctx)) || (rc = cand_check_layout(ctx, layout, "fsnap_candidate_rows"))) return rc;
+    if (!beta || P <= 0 || !out || (what != FSNAP_CAND_ERROR_SUMS && what != FSNAP_CAND_RHS) || (what == FSNAP_CAND_RHS && !S))
+        return ctx->fail(FSNAP_E_ARG, "fsnap_candidate_rows: bad argument");
+    if (ncat != ctx->cand_ncat || K_ != ctx->K)
+        return ctx->fail(FSNAP_E_ARG, "fsnap_candidate_rows: ncat = %d, K = %lld but the layout has %d, the rows %lld", ncat,
+                         (long long)K_, ctx->cand_ncat, (long long)ctx->K);
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    const int K = (int)ctx->K;
+    const int64_t K8 = (K + 7) / 8 * 8;
+    const bool sums = what == FSNAP_CAND_ERROR_SUMS;
+    const int64_t nch = sums ? ctx->cand_nch_a : ctx->cand_nch_t;
+    const int64_t nout = sums ? (int64_t)ncat * 4 : K;
+    const int64_t per = fsnap::cand_rows_partial_doubles(what, K);
+    if (!ctx->cand_betaT.ensure((size_t)K8 * 16 * 8) || !ctx->cand_rpart.ensure((size_t)(nch > 0 ? nch : 1) * per * 8) ||
+        !ctx->cand_res.ensure((size_t)P * nout * 8) || (!sums && !ctx->cand_S.ensure((size_t)P * ncat * 8)))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(candidate rows) failed");
+    if (!sums)
+        FSNAP_HIP(hipMemcpyAsync(ctx->cand_S.p, S, (size_t)P * ncat * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(S)");
+    if (nch == 0) FSNAP_HIP(hipMemsetAsync(ctx->cand_res.p, 0, (size_t)P * nout * 8, ctx->stream), "hipMemsetAsync");
+    std::vector<double> bt((size_t)K8 * 16);
+    for (int p0 = 0; p0 < P; p0 += fsnap::CAND_ROWS_MAX_P) {
+        const int np = std::min(fsnap::CAND_ROWS_MAX_P, P - p0);
+        std::fill(bt.begin(), bt.end(), 0.0);
+        for (int p = 0; p < np; ++p)
+            for (int k = 0; k < K; ++k) bt[(size_t)k * 16 + p] = beta[(int64_t)(p0 + p) * K + k];
+        // the launch before may still read betaT: the copy is ordered after it on the stream, the host buffer must outlive it
+        FSNAP_HIP(hipMemcpyAsync(ctx->cand_betaT.p, bt.data(), bt.size() * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(beta)");
+        if (nch == 0) continue;
+        FSNAP_HIP(fsnap::launch_cand_rows(what, ctx->dA, ctx->lda, ctx->db, (const double*)ctx->cand_w0.p,
+                                          (const int*)(sums ? ctx->cand_idx_a.p : ctx->cand_idx_t.p),
+                                          (const fsnap::CatChunk*)(sums ? ctx->cand_ch_a.p : ctx->cand_ch_t.p), nch, K,
+                                          (const double*)ctx->cand_betaT.p, (double*)ctx->cand_rpart.p, ctx->stream),
+                  "launch fsnap_cand_rows_k");
+        FSNAP_HIP(fsnap::launch_cand_reduce(what, (const double*)ctx->cand_rpart.p, (const int*)(sums ? ctx->cand_cb_a.p : ctx->cand_cb_t.p),
+                                            (const double*)ctx->cand_S.p, ncat, np, p0, K, (double*)ctx->cand_res.p, ctx->stream),
+                  "launch fsnap_cand_reduce_k");
+        FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");   // bt is rewritten for the next group
+    }
+    FSNAP_HIP(hipMemcpyAsync(out, ctx->cand_res.p, (size_t)P * nout * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(out)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
     return FSNAP_OK;
 }
 

@@ -105,6 +105,16 @@ struct fsnap_ctx {
     DevBuf du, dspart, dsvec;                     // refinement: row weights u, per-workgroup partials, s
     DevBuf merr_cq, merr_part, merr_out;          // fsnap_merr_eval: [c | q], partials [g | h | val] per workgroup, sums
     DevBuf merr_u, merr_vpart;                    // ... K > 288: per-row (alpha w, beta w^2), per-workgroup values
+    // batched candidate fits (fsnap_cat_prepare ... fsnap_candidate_rows, kernels of fsnap_cand.hip): row ids sorted by
+    // category and chunk lists of the training rows (_t) and of all categorised rows (_a), the base weights w0 as they were at
+    // prepare time, the per-category statistics and the candidates' packed statistics
+    DevBuf cand_idx_t, cand_idx_a, cand_ch_t, cand_ch_a, cand_cb_t, cand_cb_a, cand_w0;
+    DevBuf cand_part, cand_stats, cand_S, cand_out, cand_betaT, cand_rpart, cand_res;
+    const double* cand_dA = nullptr;              // rows the chunk lists belong to (nullptr = none prepared)
+    int64_t cand_m = 0, cand_nch_t = 0, cand_nch_a = 0;
+    int cand_ncat = 0;
+    int64_t cand_stats_K = 0;                     // order of the statistics in cand_stats (0 = none)
+    int64_t cand_layout = 0;                      // tag of the layout (fsnap_cat_prepare; 0 = none): dropped when the rows change
     double* pinned = nullptr;                     // page-locked host staging of the packed statistics: plain (coarse-grained)
                                                   // pinned memory, the target of DMA copies only -- copies into COHERENT
                                                   // host memory were bimodal (2 MB in 0.05 or in 8 ms)

@@ -151,6 +151,38 @@ hipError_t launch_merr(const double* A, int64_t lda, const double* cq, int64_t m
                        const unsigned char* mask, int method, double d, double* u, double* val_part, double* partial,
                        double* out, hipStream_t st);
 
+// Batched candidate fits (fsnap_cand.hip).  Rows are gathered through an index sorted by category and cut into chunks of
+// at most CAT_CHUNK_ROWS rows of one category; every chunk has at least one row.
+struct CatChunk {
+    int64_t first;   // position of the chunk's first row in the sorted index
+    int32_t cat;     // category of all its rows
+    int32_t count;   // rows, 1 ... CAT_CHUNK_ROWS
+};
+constexpr int CAT_CHUNK_ROWS = 1024;
+// doubles of one chunk's partial of kernel C1: tile triangle [pair][4][64] | c [NT * 16] | scalars [3]
+int cat_partial_doubles(int K);
+// kernel C1 / C1G: part[chunk][NT (NT + 1) / 2][4][64], cpart[chunk][NT * 16], spart[chunk][3] (NT = ceil(K / 16))
+hipError_t launch_cat_syrk(const double* A, int64_t lda, const double* b, const double* w0, const int* idx,
+                           const CatChunk* chunks, int64_t nchunks, int K, double* part, double* cpart, double* spart,
+                           hipStream_t st);
+// kernel C1R: stats[c][K^2 + K + 3] = packed [G | c | b^T W^2 b, sum wb, n_train] of category c; cbeg[ncat + 1] = first chunk
+hipError_t launch_cat_reduce(const double* part, const double* cpart, const double* spart, const int* cbeg, int ncat, int K,
+                             double* stats, hipStream_t st);
+// kernel C2: out[p][K^2 + K + 3] = sum_c S[p][c]^2 stats[c] (S[p][c] for sum wb, 1 for n_train)
+hipError_t launch_cand_combine(const double* stats, const double* S, int P, int ncat, int K, double* out, hipStream_t st);
+// kernel C3: at most CAND_ROWS_MAX_P candidates per launch, betaT[ceil(K / 8) * 8][16] (zero-padded);
+// what = 0: error sums over the chunks of all rows, what = 1: refinement right-hand sides over the training chunks.
+// partial: cand_rows_partial_doubles(what, K) doubles per chunk
+constexpr int CAND_ROWS_MAX_P = 16;
+int64_t cand_rows_partial_doubles(int what, int K);
+hipError_t launch_cand_rows(int what, const double* A, int64_t lda, const double* b, const double* w0, const int* idx,
+                            const CatChunk* chunks, int64_t nchunks, int K, const double* betaT, double* partial,
+                            hipStream_t st);
+// kernel C3R for the np candidates p0 ... p0 + np - 1 of one launch: what = 0: out[p][ncat][4] sums; what = 1: out[p][K] =
+// sum_c S[p][c]^2 s_c (S: [P][ncat] on the device)
+hipError_t launch_cand_reduce(int what, const double* partial, const int* cbeg, const double* S, int ncat, int np, int p0,
+                              int K, double* out, hipStream_t st);
+
 // Row-space solve (fsnap_trsm.hip).  Q <- X R^-1 by blocked substitution over the columns, one wave per 64 rows:
 // first pass X = diag(w_eff) A (src = A, leading dimension lds, per-row pairs wpack = (w_eff, w_eff b); rows with
 // w_eff = 0 become zero rows), later passes X = Q in place (src = Q, wpack = nullptr).  R: device, K16 x K16 row-major

@@ -392,6 +392,74 @@ int fsnap_rowspace_chain(int64_t K, int64_t nfac, const double* R, const unsigne
  * w_rmse = sqrt(sum (w r)^2 / n_w), ...).  Predictions (GEMV) and both reduction passes run on the GPU. */
 int fsnap_error_stats(fsnap_ctx* ctx, const double* beta, const int32_t* cat, int ncat, double* stats);
 
+/* ---- batched candidate fits of a weight search ------------------------------------------------------------------
+ * A candidate p scales the base weight w0_i of every row of category c by S[p][c] (the genetic algorithm's
+ * new_w[i] = table[group(i)][eweight | fweight | vweight], examples/library/genetic_algorithm/libmod_optimize.py).  Its
+ * statistics are then G_p = sum_c S[p][c]^2 G_c, c_p = sum_c S[p][c]^2 r_c: one pass over the rows gives the per-category
+ * G_c, r_c, and a candidate costs a C x (K^2 + K + 3) combination and a K x K solve.  Results are bit-identical run to
+ * run, and a candidate's results do not depend on the other candidates of its batch. */
+
+/* Upper bound of the per-category statistics, ncat * FSNAP_PACKED_LEN(K) * 8 bytes, and of the P candidates' packed
+ * statistics of one fsnap_fit_candidates call, P * FSNAP_PACKED_LEN(K) * 8 bytes; past it the calls return FSNAP_E_ARG. */
+#define FSNAP_CAT_STATS_MAX_BYTES ((int64_t)2 << 30)
+
+/* Work layout of the candidate kernels for the resident rows: cat[m] (host) = category id of each row in [0, ncat)
+ * (negative = the row takes no part, as in fsnap_error_stats).  The row ids are stable-sorted by category (counting sort)
+ * and cut into chunks of at most 1024 rows of one category, once for the training rows of the resident mask and once
+ * for all categorised rows; the resident weights are copied as the base weights w0.  *layout receives the tag of this
+ * layout (unique in the process); every later call of the group names it and fails with FSNAP_E_STATE when the context
+ * no longer holds it -- a context holds ONE layout: another fsnap_cat_prepare replaces it, and any change of the resident
+ * rows (fsnap_upload_rows, fsnap_bind_rows, fsnap_rows_alloc, fsnap_drop_rows, fsnap_assemble) drops it.  Mask and weights
+ * are those of this call (later changes do not reach the layout).  At most 2^31 - 1 rows.  Synchronous. */
+int fsnap_cat_prepare(fsnap_ctx* ctx, const int32_t* cat, int ncat, int64_t* layout);
+
+/* What the context holds (ctx may be NULL: the first three entries are then 0): info[0] = tag of its layout (0 = none),
+ * info[1] = its number of categories, info[2] = the order of its per-category statistics (0 = none computed yet),
+ * info[3] = rows per chunk (1024), info[4] = candidates per launch of the row kernel (16).  n <= 5 entries. */
+int fsnap_cat_info(const fsnap_ctx* ctx, int64_t* info, int n);
+
+/* The host half of fsnap_cat_prepare, no context needed: idx (capacity m) receives the ids of the rows with cat >= 0 (and
+ * mask != 0 unless mask is NULL) stably sorted by category; chunks (capacity 3 (m + ncat)) receives *nchunks triples
+ * (category, first position in idx, rows) in category order, at most 1024 rows each, none empty. */
+int fsnap_cat_chunks(int64_t m, const int32_t* cat, const uint8_t* mask, int ncat, int32_t* idx, int64_t* chunks,
+                     int64_t* nchunks);
+
+/* Per-category statistics of the training rows with the base weights, one pass over the rows (kernels C1 + C1R of
+ * csrc/fsnap_cand.hip): *d_stats (device, owned by the context, valid until the next call of this group) receives
+ * ncat blocks of FSNAP_PACKED_LEN(K) doubles, each [G_c | r_c | b^T W^2 b, sum w b, n_train] as fsnap_normal_eq_resident
+ * lays them out.  Asynchronous. */
+int fsnap_cat_normal_eq(fsnap_ctx* ctx, int64_t layout, double** d_stats);
+
+/* Multi-GPU form (collective, every rank of the communicator): each rank computes the statistics of ITS rows and one
+ * in-place all-reduce of ncat * FSNAP_PACKED_LEN(K) doubles -- the transport of fsnap_fit_dist -- leaves the sums on every
+ * rank (K and ncat must agree on all ranks).  *layout = the rank's prepared layout, or 0 on a rank without rows: it
+ * contributes zeros and receives the tag of a layout that holds the statistics only (for fsnap_fit_candidates). */
+int fsnap_cat_normal_eq_dist(fsnap_ctx* ctx, int64_t* layout, int64_t K, int ncat, double** d_stats);
+
+/* P candidates from the per-category statistics of layout `layout` (ncat categories, order K: both must be those of the
+ * statistics the context holds, else FSNAP_E_ARG; S must hold P x ncat doubles, beta P x K): kernel C2 forms
+ * G_p, c_p = sum_c S[p][c]^2 (G_c, r_c) (S: host, P x ncat, row-major), then each candidate is solved by
+ * fsnap_solve_device (K < 232 on the host, from 232 on by the device Cholesky): beta[P][K], rank[P] and rcond_est[P]
+ * exactly as fsnap_fit_resident reports them.  *d_packed (may be NULL) receives the device address of the P packed
+ * buffers (p at offset p * FSNAP_PACKED_LEN(K)), valid until the next call of this group.  Synchronous; the first solve
+ * that fails ends the call with its status. */
+int fsnap_fit_candidates(fsnap_ctx* ctx, int64_t layout, int kind, double param, const double* S, int P, int ncat, int64_t K,
+                         double* beta, int* rank, double* rcond_est, double** d_packed);
+
+/* One pass over the rows of layout `layout` (ncat and K must be its own, else FSNAP_E_ARG) for P coefficient vectors
+ * beta[P][K] (host), y_p = a . beta_p, r = t - y_p (kernel C3, at
+ * most 16 candidates per launch; more take several launches):
+ *   what = FSNAP_CAND_ERROR_SUMS: out[P][ncat][4] = sum|r|, sum r^2, sum|w0 r|, sum (w0 r)^2 over all rows of each
+ *          category (S may be NULL) -- the candidate-dependent sums of fsnap_error_stats; the weighted ones scale
+ *          with |S[p][c]| and S[p][c]^2;
+ *   what = FSNAP_CAND_RHS: out[P][K] = A^T (S[p][c(i)]^2 w0_i^2 r_i) over the training rows, fsnap_residual_rhs for P
+ *          candidates (S: host, P x ncat).
+ * Synchronous. */
+#define FSNAP_CAND_ERROR_SUMS 0
+#define FSNAP_CAND_RHS 1
+int fsnap_candidate_rows(fsnap_ctx* ctx, int64_t layout, const double* beta, const double* S, int P, int ncat, int64_t K,
+                         int what, double* out);
+
 /* ---- multi-GPU: one process per GPU; RCCL or one-shot peer-to-peer over xGMI -------- */
 
 /* The reference's data-parallel form of this path (examples/library/transpose_trick/example.py:230-254): every MPI
