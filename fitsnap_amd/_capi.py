@@ -29,6 +29,7 @@ COMM_ID_BYTES = 128
 REDUCE_SUM, REDUCE_MAX, REDUCE_MIN = 0, 1, 2
 MERR_IID, MERR_ABC, MERR_FULL = 0, 1, 2
 CAND_ERROR_SUMS, CAND_RHS = 0, 1            # fsnap_candidate_rows: what
+UQ_QUAD, UQ_NORM = 0, 1                     # fsnap_row_variance: mode
 MERR_METHODS = {"iid": MERR_IID, "abc": MERR_ABC, "full": MERR_FULL}
 
 _P_D = POINTER(c_double)
@@ -113,6 +114,10 @@ SIGNATURES = {
     "fsnap_fit_candidates": (c_int, [c_void_p, c_int64, c_int, c_double, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p,
                                      c_void_p, POINTER(c_void_p)]),
     "fsnap_candidate_rows": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p]),
+    "fsnap_row_variance": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fsnap_row_variance_device": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
@@ -746,6 +751,63 @@ class HipContext:
         return out
 
     # -- row-space least squares --------------------------------------------------------
+    def row_variance(self, M, mode=UQ_QUAD, beta=None, scale=None, cat=None, ncat=0, want_var=True, want_preds=False):
+        """One pass over the resident rows (``fsnap_row_variance``): var_i = a_i^T M a_i (``UQ_QUAD``, M is K x K) or
+        ||a_i M||^2 (``UQ_NORM``, M is K x J), preds_i = a_i . beta, and with ``cat`` (one int id per row, negative = skip)
+        per-category sum / max / count of scale_i var_i.  Returns a dict with "var", "preds", "cat_sum", "cat_max",
+        "cat_count" (None where not asked for)."""
+        mode = int(mode)
+        M = _f64(M, "M")
+        if M.ndim == 1:
+            M = M.reshape(-1, 1)
+        if M.ndim != 2:
+            raise ValueError("M must be 2-D")
+        K, J = M.shape
+        m = self.m
+        if beta is not None:
+            beta = _f64(beta, "beta").reshape(-1)
+            if beta.shape != (K,):
+                raise ValueError(f"beta has shape {beta.shape}, expected ({K},)")
+        elif want_preds:
+            raise ValueError("want_preds needs beta")
+        if scale is not None:
+            scale = _f64(scale, "scale").reshape(-1)
+            if scale.shape != (m,):
+                raise ValueError(f"scale has shape {scale.shape}, expected ({m},)")
+        ncat = int(ncat)
+        sums = maxs = counts = None
+        if cat is not None:
+            cat = np.ascontiguousarray(cat, dtype=np.int32)
+            if cat.shape != (m,):
+                raise ValueError(f"cat has shape {cat.shape}, expected ({m},)")
+            sums = np.empty(max(ncat, 0))
+            maxs = np.empty(max(ncat, 0))
+            counts = np.empty(max(ncat, 0), dtype=np.int64)
+        var = np.empty(m) if want_var else None
+        preds = np.empty(m) if want_preds else None
+        self._check(self._lib.fsnap_row_variance(self._h, mode, K, J, _ptr(M), _ptr(beta), _ptr(scale), _ptr(cat), ncat,
+                                                 _ptr(var), _ptr(preds), _ptr(sums), _ptr(maxs), _ptr(counts)))
+        return {"var": var, "preds": preds, "cat_sum": sums, "cat_max": maxs, "cat_count": counts}
+
+    def row_variance_device(self, M, mode, d_var=0, d_preds=0, beta=None, d_scale=0, cat=None, ncat=0, d_cat_sum=0,
+                            d_cat_max=0, d_cat_count=0):
+        """``fsnap_row_variance_device``: the same pass with device outputs (integer addresses, 0 = not wanted), queued on
+        the context's stream."""
+        M = _f64(M, "M")
+        if M.ndim == 1:
+            M = M.reshape(-1, 1)
+        K, J = M.shape
+        if beta is not None:
+            beta = _f64(beta, "beta").reshape(-1)
+        if cat is not None:
+            cat = np.ascontiguousarray(cat, dtype=np.int32)
+            if cat.shape != (self.m,):
+                raise ValueError(f"cat has shape {cat.shape}, expected ({self.m},)")
+        v = lambda p: c_void_p(p or None)    # noqa: E731
+        self._check(self._lib.fsnap_row_variance_device(self._h, int(mode), K, J, _ptr(M), _ptr(beta), v(d_scale), _ptr(cat),
+                                                        int(ncat), v(d_var), v(d_preds), v(d_cat_sum), v(d_cat_max),
+                                                        v(d_cat_count)))
+
     def lstsq_rows(self, rcond: float, K: int = None):
         """``lstsq(aw, bw, rcond)`` of the resident rows computed on the rows (fsnap_lstsq_rows); collective when the
         context has a communicator.  Returns (beta, rank, info dict)."""

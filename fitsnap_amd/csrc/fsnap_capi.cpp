@@ -2281,3 +2281,160 @@ int fsnap_candidate_rows(fsnap_ctx* ctx, int64_t layout, const double* beta, con
 }
 
 }  // extern "C"
+
+// ---- predictive variance of the resident rows (kernels U1 / U1G, U2, U3 of fsnap_uq.hip) ----------------------------
+
+namespace {
+
+// dev_out: var / preds / cat_sum / cat_max / cat_count are device pointers and the call returns once the work is queued;
+// scale is then a device pointer too.  Otherwise everything is host memory and the call is synchronous.
+int row_variance(fsnap_ctx* ctx, int mode, int64_t K, int64_t J, const double* M, const double* beta, const double* scale,
+                 const int32_t* cat, int ncat, double* var, double* preds, double* cat_sum, double* cat_max,
+                 int64_t* cat_count, bool dev_out) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = dev_out ? "fsnap_row_variance_device" : "fsnap_row_variance";
+    if (mode != FSNAP_UQ_QUAD && mode != FSNAP_UQ_NORM) return ctx->fail(FSNAP_E_ARG, "%s: unknown mode %d", who, mode);
+    const bool want_cat = cat != nullptr;
+    if (want_cat && ncat <= 0) return ctx->fail(FSNAP_E_ARG, "%s: cat given with ncat = %d", who, ncat);
+    if (!want_cat && (cat_sum || cat_max || cat_count))
+        return ctx->fail(FSNAP_E_ARG, "%s: category outputs without categories", who);
+    const bool need_v = var || want_cat;
+    if (need_v && !M) return ctx->fail(FSNAP_E_ARG, "%s: M is NULL", who);
+    if (preds && !beta) return ctx->fail(FSNAP_E_ARG, "%s: preds wanted but beta is NULL", who);
+    if (J < 1 || J > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: J = %lld", who, (long long)J);
+    if (mode == FSNAP_UQ_QUAD && J != K)
+        return ctx->fail(FSNAP_E_ARG, "%s: QUAD needs J = K (J = %lld, K = %lld)", who, (long long)J, (long long)K);
+    const int64_t m = ctx->m;
+    if (m > 0 && K != ctx->K)        // no rows (a rank that owns none): nothing to check K against
+        return ctx->fail(FSNAP_E_ARG, "%s: K = %lld, the resident rows have %lld columns", who, (long long)K, (long long)ctx->K);
+    if (K < 1 || K > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: K = %lld", who, (long long)K);
+    if (want_cat && m > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: categories need m < 2^31", who);
+    if (m > 0) {
+        int rc = check_rows(ctx);
+        if (rc) return rc;
+    }
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    if (ctx->uq_inflight) {
+        FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+        ctx->uq_inflight = false;
+    }
+    // categories first: an id >= ncat is an argument error before anything is queued
+    int64_t nch = 0;
+    if (want_cat) {
+        ctx->uq_hidx.resize((size_t)std::max<int64_t>(m, 1));
+        ctx->uq_hch.resize(3 * (size_t)(m + ncat));
+        if (fsnap_cat_chunks(m, cat, nullptr, ncat, ctx->uq_hidx.data(), ctx->uq_hch.data(), &nch) != FSNAP_OK)
+            return ctx->fail(FSNAP_E_ARG, "%s: %s", who, fsnap::library_error().c_str());
+        ctx->uq_hcount.assign((size_t)ncat, 0);
+        ctx->uq_hcbeg.assign((size_t)ncat + 1, 0);
+        // CatChunk records in place of the triples (16 bytes each: first, then category and count as int32)
+        std::vector<int64_t>& h = ctx->uq_hch;
+        for (int64_t i = 0; i < nch; ++i) {
+            const int64_t c = h[3 * i], first = h[3 * i + 1], cnt = h[3 * i + 2];
+            ctx->uq_hcount[(size_t)c] += cnt;
+            ctx->uq_hcbeg[(size_t)c + 1] += 1;
+            fsnap::CatChunk rec{first, (int32_t)c, (int32_t)cnt};
+            std::memcpy(&h[2 * i], &rec, sizeof rec);
+        }
+        for (int c = 0; c < ncat; ++c) ctx->uq_hcbeg[(size_t)c + 1] += ctx->uq_hcbeg[(size_t)c];
+    }
+    const int64_t Kp = (K + 15) / 16 * 16, Jp = (J + 15) / 16 * 16;
+    double* dvar = nullptr;
+    double* dpreds = nullptr;
+    if (m > 0 && (need_v || preds)) {
+        // staging [M padded to Kp x Jp | beta padded to Kp], one copy up
+        const size_t nM = (size_t)(Kp * Jp);
+        ctx->uq_hM.assign(nM + (size_t)Kp, 0.0);
+        if (need_v)
+            for (int64_t k = 0; k < K; ++k) std::memcpy(&ctx->uq_hM[(size_t)(k * Jp)], M + k * J, (size_t)J * 8);
+        if (preds) std::memcpy(&ctx->uq_hM[nM], beta, (size_t)K * 8);
+        if (!ctx->uq_M.ensure((nM + (size_t)Kp) * 8)) return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(uq) failed");
+        FSNAP_HIP(hipMemcpyAsync(ctx->uq_M.p, ctx->uq_hM.data(), (nM + (size_t)Kp) * 8, hipMemcpyHostToDevice, ctx->stream),
+                  "hipMemcpy(M)");
+        if (need_v) {
+            if (dev_out && var) {
+                dvar = var;
+            } else {
+                if (!ctx->uq_var.ensure((size_t)m * 8)) return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(var) failed");
+                dvar = (double*)ctx->uq_var.p;
+            }
+        }
+        if (preds) {
+            if (dev_out) {
+                dpreds = preds;
+            } else {
+                if (!ctx->uq_preds.ensure((size_t)m * 8)) return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(preds) failed");
+                dpreds = (double*)ctx->uq_preds.p;
+            }
+        }
+        FSNAP_HIP(fsnap::launch_uq_rows(mode == FSNAP_UQ_QUAD ? fsnap::UQ_QUAD : fsnap::UQ_NORM, ctx->dA, ctx->lda, m, (int)K,
+                                        (const double*)ctx->uq_M.p, (int)Jp, (const double*)ctx->uq_M.p + Kp * Jp, dvar, dpreds,
+                                        ctx->stream),
+                  "launch fsnap_uq_rows_k");
+    }
+    double* dsum = nullptr;
+    double* dmax = nullptr;
+    if (want_cat) {
+        if (!ctx->uq_idx.ensure((size_t)std::max<int64_t>(m, 1) * 4) || !ctx->uq_ch.ensure((size_t)std::max<int64_t>(nch, 1) * 16) ||
+            !ctx->uq_cbeg.ensure(((size_t)ncat + 1) * 4) || !ctx->uq_part.ensure((size_t)std::max<int64_t>(nch, 1) * 16) ||
+            (!dev_out && !ctx->uq_cat.ensure((size_t)ncat * 16)) || (scale && !dev_out && !ctx->uq_scale.ensure((size_t)m * 8 + 8)))
+            return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(uq categories) failed");
+        if (m > 0) {
+            FSNAP_HIP(hipMemcpyAsync(ctx->uq_idx.p, ctx->uq_hidx.data(), (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream),
+                      "hipMemcpy(idx)");
+        }
+        if (nch > 0)
+            FSNAP_HIP(hipMemcpyAsync(ctx->uq_ch.p, ctx->uq_hch.data(), (size_t)nch * 16, hipMemcpyHostToDevice, ctx->stream),
+                      "hipMemcpy(chunks)");
+        FSNAP_HIP(hipMemcpyAsync(ctx->uq_cbeg.p, ctx->uq_hcbeg.data(), ((size_t)ncat + 1) * 4, hipMemcpyHostToDevice, ctx->stream),
+                  "hipMemcpy(cbeg)");
+        const double* dscale = nullptr;
+        if (scale && m > 0) {
+            if (dev_out) {
+                dscale = scale;
+            } else {
+                FSNAP_HIP(hipMemcpyAsync(ctx->uq_scale.p, scale, (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream),
+                          "hipMemcpy(scale)");
+                dscale = (const double*)ctx->uq_scale.p;
+            }
+        }
+        dsum = dev_out ? cat_sum : (double*)ctx->uq_cat.p;
+        dmax = dev_out ? cat_max : (double*)ctx->uq_cat.p + ncat;
+        FSNAP_HIP(fsnap::launch_uq_cat(dvar, dscale, (const int*)ctx->uq_idx.p, (const fsnap::CatChunk*)ctx->uq_ch.p,
+                                       m > 0 ? nch : 0, (const int*)ctx->uq_cbeg.p, ncat, (double*)ctx->uq_part.p, dsum, dmax,
+                                       ctx->stream),
+                  "launch fsnap_uq_chunk_k");
+        if (cat_count) {
+            if (dev_out)
+                FSNAP_HIP(hipMemcpyAsync(cat_count, ctx->uq_hcount.data(), (size_t)ncat * 8, hipMemcpyHostToDevice, ctx->stream),
+                          "hipMemcpy(cat_count)");
+            else
+                std::memcpy(cat_count, ctx->uq_hcount.data(), (size_t)ncat * 8);
+        }
+    }
+    if (dev_out) {
+        ctx->uq_inflight = true;
+        return FSNAP_OK;
+    }
+    if (var && m > 0) FSNAP_HIP(hipMemcpyAsync(var, dvar, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(var)");
+    if (preds && m > 0)
+        FSNAP_HIP(hipMemcpyAsync(preds, dpreds, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(preds)");
+    if (cat_sum) FSNAP_HIP(hipMemcpyAsync(cat_sum, dsum, (size_t)ncat * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(sum)");
+    if (cat_max) FSNAP_HIP(hipMemcpyAsync(cat_max, dmax, (size_t)ncat * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(max)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    return FSNAP_OK;
+}
+
+}  // namespace
+
+int fsnap_row_variance(fsnap_ctx* ctx, int mode, int64_t K, int64_t J, const double* M, const double* beta, const double* scale,
+                       const int32_t* cat, int ncat, double* var, double* preds, double* cat_sum, double* cat_max,
+                       int64_t* cat_count) {
+    return row_variance(ctx, mode, K, J, M, beta, scale, cat, ncat, var, preds, cat_sum, cat_max, cat_count, false);
+}
+
+int fsnap_row_variance_device(fsnap_ctx* ctx, int mode, int64_t K, int64_t J, const double* M, const double* beta,
+                              const double* d_scale, const int32_t* cat, int ncat, double* d_var, double* d_preds,
+                              double* d_cat_sum, double* d_cat_max, int64_t* d_cat_count) {
+    return row_variance(ctx, mode, K, J, M, beta, d_scale, cat, ncat, d_var, d_preds, d_cat_sum, d_cat_max, d_cat_count, true);
+}

@@ -115,6 +115,13 @@ struct fsnap_ctx {
     int cand_ncat = 0;
     int64_t cand_stats_K = 0;                     // order of the statistics in cand_stats (0 = none)
     int64_t cand_layout = 0;                      // tag of the layout (fsnap_cat_prepare; 0 = none): dropped when the rows change
+    // fsnap_row_variance*: [padded M | padded beta], per-row results, category layout (sorted index, chunks, first chunk per
+    // category), chunk partials, per-category results, host staging of what is copied up (kept until the copies are done)
+    DevBuf uq_M, uq_var, uq_preds, uq_scale, uq_idx, uq_ch, uq_cbeg, uq_part, uq_cat, uq_count;
+    std::vector<double> uq_hM;
+    std::vector<int32_t> uq_hidx, uq_hcbeg;
+    std::vector<int64_t> uq_hch, uq_hcount;
+    bool uq_inflight = false;                     // copies out of the staging above may still be running
     double* pinned = nullptr;                     // page-locked host staging of the packed statistics: plain (coarse-grained)
                                                   // pinned memory, the target of DMA copies only -- copies into COHERENT
                                                   // host memory were bimodal (2 MB in 0.05 or in 8 ms)

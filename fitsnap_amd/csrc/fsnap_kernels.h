@@ -183,6 +183,19 @@ hipError_t launch_cand_rows(int what, const double* A, int64_t lda, const double
 hipError_t launch_cand_reduce(int what, const double* partial, const int* cbeg, const double* S, int ncat, int np, int p0,
                               int K, double* out, hipStream_t st);
 
+// Predictive variance of rows (fsnap_uq.hip).  Mp: device, Kp x Jp row-major with Kp = 16 ceil(K / 16), Jp = 16 ceil(J / 16),
+// zero outside the K x J matrix; bp: device, Kp doubles (beta, zero-padded), read only when preds != nullptr.
+// var[m] (may be nullptr): QUAD a^T M a (J = K), NORM ||a M||^2; preds[m] (may be nullptr): a . beta.
+constexpr int UQ_QUAD = 0;
+constexpr int UQ_NORM = 1;
+hipError_t launch_uq_rows(int mode, const double* A, int64_t lda, int64_t m, int K, const double* Mp, int Jp, const double* bp,
+                          double* var, double* preds, hipStream_t st);
+// kernels U2 + U3: per-category sum / max of scale_i var_i (scale may be nullptr) over the chunks of a category-sorted index
+// (fsnap_cat_chunks); part: 2 nchunks doubles of scratch; cbeg[ncat + 1] = first chunk of each category; cat_sum / cat_max
+// (ncat, either may be nullptr)
+hipError_t launch_uq_cat(const double* var, const double* scale, const int* idx, const CatChunk* chunks, int64_t nchunks,
+                         const int* cbeg, int ncat, double* part, double* cat_sum, double* cat_max, hipStream_t st);
+
 // Row-space solve (fsnap_trsm.hip).  Q <- X R^-1 by blocked substitution over the columns, one wave per 64 rows:
 // first pass X = diag(w_eff) A (src = A, leading dimension lds, per-row pairs wpack = (w_eff, w_eff b); rows with
 // w_eff = 0 become zero rows), later passes X = Q in place (src = Q, wpack = nullptr).  R: device, K16 x K16 row-major

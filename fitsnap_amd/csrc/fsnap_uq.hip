@@ -1,0 +1,253 @@
+// fsnap_uq.hip — predictive variance of rows under a posterior covariance, one pass over the rows (gfx950 only).
+//
+// For every row a_i of A (m x K, leading dimension lda) and a small matrix M (K x J):
+//   QUAD (J = K)  v_i = a_i^T M a_i        fullcov / loop (solver.py:440-472), (A C * A).sum(-1) of the AL loop
+//   NORM          v_i = || a_i M ||^2      chol / choleye / svd / sam with M = L, shifted L, U sqrt(S), centred samples
+// and optionally p_i = a_i . beta (the predictive mean) from the same read of the row.
+//
+//   U1  fsnap_uq_rows_k<NT, MODE>  K <= 144 (NT = ceil(K / 16) <= 9): a wave takes 2 blocks of 16 rows and keeps them in
+//                                  registers for the whole pass (2 x 4 NT doubles per lane); T^T = M^T A_blk^T runs on
+//                                  v_mfma_f64_16x16x4f64 one 16-column tile of M at a time: the A operand is the M tile
+//                                  (lane (e, ks): M[4 s + ks][16 jt + e]), the B operand is the row block as it stands
+//                                  (lane (e, ks): a_e[4 s + ks]), so D[reg g] at lane (e, ks) is T[e][16 jt + ks + 4 g].
+//                                  The QUAD epilogue needs a_e[16 jt + ks + 4 g], a value of the same lane's row (re-read
+//                                  from L1 / L2: keeping it in a register needs the tile loop unrolled, which spills).
+//                                  The two row blocks share every M fragment (two independent accumulator chains).
+//   U1G fsnap_uq_rows_gen_k<MODE>  K > 144 (untuned): the same tiles with the row values re-read (L1 / L2) per M tile
+//   U2  fsnap_uq_chunk_k           per chunk of the category-sorted row index (fsnap_cat_chunks): sum and max of s_i v_i
+//   U3  fsnap_uq_cat_k             per category: the chunks' sums in chunk order, their max
+// T is never stored.  A row's result is a function of a_i, M, beta alone: its lane position within the block changes
+// nothing (every D element is the same MFMA k-chain, the fold is per lane in a fixed order, then xor 16, xor 32), so results
+// are bit-identical under any row subset, permutation, m or lda.  Category sums follow the stable-sorted row order.  No
+// atomics; every result is written with vector stores.
+#include "fsnap_device_common.h"
+#include "fsnap_kernels.h"
+
+namespace {
+
+constexpr int UQ_RB = 2;   // 16-row blocks per wave
+
+template <int MODE>
+__device__ __forceinline__ double uq_fold(double v, double t, double a) {
+    if constexpr (MODE == fsnap::UQ_QUAD) return __builtin_fma(t, a, v);
+    else return __builtin_fma(t, t, v);
+}
+
+// sum over the four lanes e, e + 16, e + 32, e + 48 (fixed order)
+__device__ __forceinline__ double uq_ks_sum(double v) {
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    return v;
+}
+
+template <int NT, int MODE>
+__global__ __launch_bounds__(256, 2) void fsnap_uq_rows_k(const double* __restrict__ A, int64_t lda, int64_t m, int K,
+                                                       const double* __restrict__ Mp, int Jp,
+                                                       const double* __restrict__ bp, double* __restrict__ var,
+                                                       double* __restrict__ preds) {
+    constexpr int NS = 4 * NT;
+    const int lane = threadIdx.x & 63, e = lane & 15, ks = lane >> 4, wave = threadIdx.x >> 6;
+    const int64_t row0 = ((int64_t)blockIdx.x * 4 + wave) * (16 * UQ_RB);
+    double x[UQ_RB][NS];
+    int64_t row[UQ_RB];
+    bool valid[UQ_RB];
+#pragma unroll
+    for (int r = 0; r < UQ_RB; ++r) {
+        row[r] = row0 + 16 * r + e;
+        valid[r] = row[r] < m;
+        const double* src = A + (valid[r] ? row[r] : 0) * lda;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int k = 4 * s + ks;
+            double v = 0.0;
+            if (valid[r] && k < K) v = src[k];
+            x[r][s] = v;
+        }
+    }
+    if (preds) {
+#pragma unroll
+        for (int r = 0; r < UQ_RB; ++r) {
+            double p = 0.0;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) p = __builtin_fma(x[r][s], bp[4 * s + ks], p);
+            p = uq_ks_sum(p);
+            if (ks == 0 && valid[r]) preds[row[r]] = p;
+        }
+    }
+    if (!var) return;
+    double v[UQ_RB];
+#pragma unroll
+    for (int r = 0; r < UQ_RB; ++r) v[r] = 0.0;
+    // one 16-column tile of M per step (a runtime loop: unrolling it over the tiles to keep the QUAD epilogue's row values
+    // in registers spills at NT >= 8); the QUAD epilogue re-reads a_e[16 jt + ks + 4 g] (L1 / L2, the row was just read)
+    const double* src[UQ_RB];
+#pragma unroll
+    for (int r = 0; r < UQ_RB; ++r) src[r] = A + (valid[r] ? row[r] : 0) * lda;
+    const int njt = Jp / 16;
+    for (int jt = 0; jt < njt; ++jt) {
+        d4 acc[UQ_RB];
+#pragma unroll
+        for (int r = 0; r < UQ_RB; ++r) acc[r] = d4{0.0, 0.0, 0.0, 0.0};
+        const double* mcol = Mp + 16 * jt + e;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const double mf = mcol[(int64_t)(4 * s + ks) * Jp];
+#pragma unroll
+            for (int r = 0; r < UQ_RB; ++r) acc[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(mf, x[r][s], acc[r], 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < UQ_RB; ++r)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                double a = 0.0;
+                if constexpr (MODE == fsnap::UQ_QUAD) {
+                    const int k = 16 * jt + ks + 4 * g;
+                    if (valid[r] && k < K) a = src[r][k];
+                }
+                v[r] = uq_fold<MODE>(v[r], acc[r][g], a);     // NORM: padding columns of M are zero, they add nothing
+            }
+    }
+#pragma unroll
+    for (int r = 0; r < UQ_RB; ++r) {
+        const double s = uq_ks_sum(v[r]);
+        if (ks == 0 && valid[r]) var[row[r]] = s;
+    }
+}
+
+// Kernel U1G: any K (untuned).  Same lane mapping; the row values are loaded per k step of every M tile.
+template <int MODE>
+__global__ __launch_bounds__(256) void fsnap_uq_rows_gen_k(const double* __restrict__ A, int64_t lda, int64_t m, int K,
+                                                           const double* __restrict__ Mp, int Jp,
+                                                           const double* __restrict__ bp, double* __restrict__ var,
+                                                           double* __restrict__ preds) {
+    const int lane = threadIdx.x & 63, e = lane & 15, ks = lane >> 4, wave = threadIdx.x >> 6;
+    const int64_t row0 = ((int64_t)blockIdx.x * 4 + wave) * (16 * UQ_RB);
+    const int ns = (K + 3) / 4;
+    const double* src[UQ_RB];
+    int64_t row[UQ_RB];
+    bool valid[UQ_RB];
+#pragma unroll
+    for (int r = 0; r < UQ_RB; ++r) {
+        row[r] = row0 + 16 * r + e;
+        valid[r] = row[r] < m;
+        src[r] = A + (valid[r] ? row[r] : 0) * lda;
+    }
+    auto ld = [&](int r, int k) -> double { return (valid[r] && k < K) ? src[r][k] : 0.0; };
+    if (preds) {
+#pragma unroll
+        for (int r = 0; r < UQ_RB; ++r) {
+            double p = 0.0;
+            for (int s = 0; s < ns; ++s) p = __builtin_fma(ld(r, 4 * s + ks), bp[4 * s + ks], p);
+            p = uq_ks_sum(p);
+            if (ks == 0 && valid[r]) preds[row[r]] = p;
+        }
+    }
+    if (!var) return;
+    double v[UQ_RB];
+#pragma unroll
+    for (int r = 0; r < UQ_RB; ++r) v[r] = 0.0;
+    const int njt = Jp / 16;
+    for (int jt = 0; jt < njt; ++jt) {
+        d4 acc[UQ_RB];
+#pragma unroll
+        for (int r = 0; r < UQ_RB; ++r) acc[r] = d4{0.0, 0.0, 0.0, 0.0};
+        const double* mcol = Mp + 16 * jt + e;
+        for (int s = 0; s < ns; ++s) {
+            const double mf = mcol[(int64_t)(4 * s + ks) * Jp];
+#pragma unroll
+            for (int r = 0; r < UQ_RB; ++r) acc[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(mf, ld(r, 4 * s + ks), acc[r], 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < UQ_RB; ++r)
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                v[r] = uq_fold<MODE>(v[r], acc[r][g], MODE == fsnap::UQ_QUAD ? ld(r, 16 * jt + ks + 4 * g) : 0.0);
+    }
+#pragma unroll
+    for (int r = 0; r < UQ_RB; ++r) {
+        const double s = uq_ks_sum(v[r]);
+        if (ks == 0 && valid[r]) var[row[r]] = s;
+    }
+}
+
+// Kernel U2: one wave per chunk; lane l takes positions l, l + 64, ... of the chunk in order, then a fixed butterfly.
+// part[chunk][2] = (sum, max) of s_i v_i over the chunk's rows (s = 1 without a scale).
+__global__ __launch_bounds__(64) void fsnap_uq_chunk_k(const double* __restrict__ var, const double* __restrict__ scale,
+                                                       const int* __restrict__ idx, const fsnap::CatChunk* __restrict__ chunks,
+                                                       double* __restrict__ part) {
+    const fsnap::CatChunk ch = chunks[blockIdx.x];
+    const int lane = threadIdx.x;
+    double s = 0.0, mx = -__builtin_inf();
+    for (int p = lane; p < ch.count; p += 64) {
+        const int r = idx[ch.first + p];
+        const double val = scale ? scale[r] * var[r] : var[r];
+        s += val;
+        mx = val > mx ? val : mx;
+    }
+    for (int o = 1; o < 64; o <<= 1) {
+        s += __shfl_xor(s, o, 64);
+        const double om = __shfl_xor(mx, o, 64);
+        mx = om > mx ? om : mx;
+    }
+    if (lane == 0) {
+        part[2 * (int64_t)blockIdx.x] = s;
+        part[2 * (int64_t)blockIdx.x + 1] = mx;
+    }
+}
+
+// Kernel U3: one thread per category, its chunks in order (cbeg[ncat + 1]); an empty category gets (0, -inf).
+__global__ __launch_bounds__(256) void fsnap_uq_cat_k(const double* __restrict__ part, const int* __restrict__ cbeg, int ncat,
+                                                     double* __restrict__ cat_sum, double* __restrict__ cat_max) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= ncat) return;
+    double s = 0.0, mx = -__builtin_inf();
+    for (int ch = cbeg[c]; ch < cbeg[c + 1]; ++ch) {
+        s += part[2 * (int64_t)ch];
+        const double om = part[2 * (int64_t)ch + 1];
+        mx = om > mx ? om : mx;
+    }
+    if (cat_sum) cat_sum[c] = s;
+    if (cat_max) cat_max[c] = mx;
+}
+
+}  // namespace
+
+namespace fsnap {
+
+hipError_t launch_uq_rows(int mode, const double* A, int64_t lda, int64_t m, int K, const double* Mp, int Jp, const double* bp,
+                          double* var, double* preds, hipStream_t st) {
+    if (m <= 0) return hipSuccess;
+    const int64_t rows_per_block = 4 * 16 * UQ_RB;
+    const dim3 grid((unsigned)((m + rows_per_block - 1) / rows_per_block));
+    const int NT = (K + 15) / 16;
+#define FSNAP_UQ_CASE(N)                                                                                   \
+    case N:                                                                                                \
+        if (mode == UQ_QUAD) fsnap_uq_rows_k<N, UQ_QUAD><<<grid, 256, 0, st>>>(A, lda, m, K, Mp, Jp, bp, var, preds); \
+        else fsnap_uq_rows_k<N, UQ_NORM><<<grid, 256, 0, st>>>(A, lda, m, K, Mp, Jp, bp, var, preds);              \
+        break;
+    switch (NT) {
+        FSNAP_UQ_CASE(1)
+        FSNAP_UQ_CASE(2)
+        FSNAP_UQ_CASE(3)
+        FSNAP_UQ_CASE(4)
+        FSNAP_UQ_CASE(5)
+        FSNAP_UQ_CASE(6)
+        FSNAP_UQ_CASE(7)
+        FSNAP_UQ_CASE(8)
+        FSNAP_UQ_CASE(9)
+        default:
+            if (mode == UQ_QUAD) fsnap_uq_rows_gen_k<UQ_QUAD><<<grid, 256, 0, st>>>(A, lda, m, K, Mp, Jp, bp, var, preds);
+            else fsnap_uq_rows_gen_k<UQ_NORM><<<grid, 256, 0, st>>>(A, lda, m, K, Mp, Jp, bp, var, preds);
+    }
+#undef FSNAP_UQ_CASE
+    return hipGetLastError();
+}
+
+hipError_t launch_uq_cat(const double* var, const double* scale, const int* idx, const CatChunk* chunks, int64_t nchunks,
+                         const int* cbeg, int ncat, double* part, double* cat_sum, double* cat_max, hipStream_t st) {
+    if (nchunks > 0) fsnap_uq_chunk_k<<<dim3((unsigned)nchunks), 64, 0, st>>>(var, scale, idx, chunks, part);
+    fsnap_uq_cat_k<<<dim3((unsigned)((ncat + 255) / 256)), 256, 0, st>>>(part, cbeg, ncat, cat_sum, cat_max);
+    return hipGetLastError();
+}
+
+}  // namespace fsnap

@@ -25,6 +25,7 @@ import numpy as np
 
 from .. import _capi
 from .._hostblas import blas_threads
+from . import uq
 
 
 class _TrainWeights:
@@ -169,6 +170,8 @@ class Solver:
         self.last_rcond = None
         self.last_refine_steps = 0   # refinement steps the last fit actually took (<= refine_steps)
         self.last_row_space = None   # diagnostics of the last row-space solve (passes, deviation, ...), or None
+        self._uq_ctx = None          # second context for explicit rows of _compute_stdev / prediction_variance
+        self._uq_key = None          # (array object it holds,)
         self._checks()
 
     # ------------------------------------------------------------------------------
@@ -240,6 +243,7 @@ class Solver:
         self._cat_ctx = None
         self._err_layout = None
         self._all_idx = None
+        self._uq_key = None
 
     def _training_mask(self, a, fs_dict, trainall):
         """svd.py:35-40 / ridge.py:28-33."""
@@ -968,3 +972,109 @@ class Solver:
             if (self.config.sections["CALCULATOR"].calculator == "LAMMPSSNAP"
                     and "BISPECTRUM" in self.config.sections and self.config.sections["BISPECTRUM"].bzeroflag):
                 self._offset()
+
+    # ------------------------------------------------------------------------------
+    # predictive uncertainty (solver.py:440-472; bayesian_active_learning.py:180-282, 820-830)
+    # ------------------------------------------------------------------------------
+    def _b0_layout(self):
+        """(ntypes, ncoeff) when ``_offset`` may have put B0 zeros into ``fit`` / ``fit_sam`` (SNAP with bzeroflag)."""
+        sec = self.config.sections
+        if (sec["CALCULATOR"].calculator == "LAMMPSSNAP" and "BISPECTRUM" in sec and sec["BISPECTRUM"].bzeroflag):
+            return sec["BISPECTRUM"].numtypes, sec["BISPECTRUM"].ncoeff
+        return None
+
+    def _uq_inputs(self):
+        """(cov, fit, fit_sam) as the rows see them: broadcast from rank 0 (where the fit lives) when several ranks take
+        part, the B0 zeros of ``_offset`` taken out by its own layout."""
+        pt = self.pt
+        cov, fit, sam = self.cov, self.fit, self.fit_sam
+        if pt.multi:
+            cov, fit, sam = pt.bcast_object((cov, fit, sam), src=0)
+        lay = self._b0_layout()
+        if lay is not None:
+            if fit is not None:
+                fit = uq.strip_b0(fit, *lay)
+            if sam is not None:
+                sam = uq.strip_b0(sam, *lay, samples=True)
+        if fit is not None:
+            fit = np.asarray(fit, dtype=np.float64).reshape(-1)
+        return cov, fit, sam
+
+    def _uq_rows(self, a):
+        """Context that holds the rows: ``a=None`` -> the shared rows on this rank's context (as ``predict_rows``);
+        an explicit array -> a second context owned by the solver, so that the training rows stay resident for the next
+        fit.  The same array object is uploaded once (changed in place, it needs ``invalidate_row_caches``)."""
+        if a is None:
+            sa, sb = self.pt.shared_arrays["a"].array, self.pt.shared_arrays["b"].array
+            return self._upload(sa, sb, True)
+        key = self._uq_key
+        if key is not None and key[0] is a and self._uq_ctx is not None:
+            return self._uq_ctx
+        arr = np.asarray(a)
+        if arr.ndim != 2:
+            raise ValueError("a must be 2-D")
+        if self._uq_ctx is None:
+            self._uq_ctx = _capi.HipContext(self.pt.device_index())
+        if arr.shape[0] == 0:
+            self._uq_ctx.drop_rows()
+            self._uq_ctx.K = arr.shape[1]
+        else:
+            self._uq_ctx.upload_rows(arr, np.zeros(arr.shape[0]))
+        self._uq_key = (a,)
+        return self._uq_ctx
+
+    def _uq_pass(self, a, method, beta=None, cat=None, ncat=0, scale=None):
+        cov, fit, sam = self._uq_inputs()
+        op = uq.stdev_operator(method, cov, sam)
+        ctx = self._uq_rows(a)
+        if op is None:                       # the reference's `else`: zeros
+            mode, M, zero = uq.NORM, np.zeros((ctx.K, 1)), True
+        else:
+            (mode, M), zero = op, False
+        out = ctx.row_variance(M, mode, beta=fit if beta else None, scale=scale, cat=cat, ncat=ncat,
+                               want_var=True, want_preds=bool(beta))
+        if zero:
+            out["var"][:] = 0.0
+        return out
+
+    def _compute_stdev(self, a=None, method="chol"):
+        """Predictive standard deviation of every row (the reference's ``Solver._compute_stdev``, solver.py:440-472), one
+        GPU pass: ``sam``, ``chol``, ``choleye``, ``svd``, ``loop``, ``fullcov``; any other method gives zeros.  ``a=None``
+        uses the resident shared rows; with several ranks each rank gets its own rows' values, in row order.  Unlike the
+        reference, ``sam`` (and every method) also works after ``error_analysis`` has put the bzeroflag B0 zeros into
+        ``fit_sam``: they are taken out again."""
+        with np.errstate(invalid="ignore"):
+            return np.sqrt(self._uq_pass(a, method)["var"])
+
+    def prediction_variance(self, a=None, categories=None, row_scale=None, method="fullcov", want_preds=True):
+        """Predictive mean and variance of every row plus per-category sums of the scaled variance -- the ranking step of
+        the Bayesian active-learning loop (bayesian_active_learning.py:180-282, 820-830) in one pass over the rows.
+
+        ``categories``: None, int ids per row (negative = skip), one label per row, or a tuple of per-row label columns
+        such as (groups, configs).  ``row_scale``: per-row factors s_i of the category sums (E/F/S reweighting, DFT cost).
+        Returns a dict: "preds" (a . fit, or None), "var" (unscaled), "keys" (the category of each slot: labels in
+        first-seen order, or range(ncat) for ids), "cat_sum", "cat_max", "cat_count" and "cat_mean" of s_i var_i."""
+        cat = keys = None
+        ncat = 0
+        if categories is not None:
+            arr = None if isinstance(categories, tuple) else np.asarray(categories)
+            if arr is not None and arr.ndim == 1 and np.issubdtype(arr.dtype, np.integer):
+                cat = arr.astype(np.int32)
+                ncat = int(cat.max()) + 1 if cat.size and cat.max() >= 0 else 0
+                keys = list(range(ncat))
+            else:
+                cat, keys = uq.category_ids(categories)
+                ncat = len(keys)
+            if ncat == 0:
+                cat = None
+        out = self._uq_pass(a, method, beta=want_preds, cat=cat, ncat=ncat, scale=row_scale)
+        res = {"preds": out["preds"], "var": out["var"], "keys": keys, "cat_sum": None, "cat_max": None,
+               "cat_count": None, "cat_mean": None}
+        if categories is not None:
+            if cat is None:
+                res.update(cat_sum=np.zeros(0), cat_max=np.zeros(0), cat_count=np.zeros(0, dtype=np.int64))
+            else:
+                res.update(cat_sum=out["cat_sum"], cat_max=out["cat_max"], cat_count=out["cat_count"])
+            with np.errstate(invalid="ignore", divide="ignore"):
+                res["cat_mean"] = res["cat_sum"] / res["cat_count"]
+        return res

@@ -274,6 +274,32 @@ int fsnap_residual_rhs(fsnap_ctx* ctx, const double* beta, double* s, double* ss
 int fsnap_merr_eval(fsnap_ctx* ctx, int method, int64_t K, const double* c, const double* q, double d, double* val,
                     double* g, double* h);
 
+/* Predictive variance of the resident rows under a posterior covariance (Solver._compute_stdev, solver.py:440-472; the
+ * ranking pass of the Bayesian active-learning loop, bayesian_active_learning.py:826-828), one pass over the rows (kernels
+ * U1 / U1G of csrc/fsnap_uq.hip, fp64 MFMA).  M (host, K x J row-major) is copied to the device on every call; per row a_i:
+ *   mode FSNAP_UQ_QUAD (J = K):  var_i = a_i^T M a_i           (fullcov / loop with M = cov)
+ *   mode FSNAP_UQ_NORM (J >= 1): var_i = ||a_i M||^2            (chol / choleye / svd with M = L, shifted L, U sqrt(S);
+ *                                                               sam with M = centred samples^T / sqrt(nsam))
+ * preds_i = a_i . beta from the same read (beta: host, K; needed only for preds).  var is NOT scaled.  With cat[m] (host,
+ * int32, id in [0, ncat), negative = the row takes no part; rows of a category need not be adjacent) kernels U2 + U3 give
+ * cat_sum[c] = sum of scale_i var_i over the rows of category c in stable-sorted row order (fsnap_cat_chunks), cat_max[c]
+ * their max and cat_count[c] their number (scale: m doubles, NULL = 1; an empty category: sum 0, max -inf, count 0).
+ * Every output may be NULL; category outputs need cat.  K must equal the resident rows' width, J = K in QUAD mode, every
+ * id must be < ncat: else FSNAP_E_ARG.  m = 0 is a no-op (category outputs are those of empty categories).  A row's result
+ * depends only on a_i, M, beta (and s_i): bit-identical run to run and under any row subset, order, m or lda.  No atomics.
+ * Host in and out, synchronous. */
+#define FSNAP_UQ_QUAD 0
+#define FSNAP_UQ_NORM 1
+int fsnap_row_variance(fsnap_ctx* ctx, int mode, int64_t K, int64_t J, const double* M, const double* beta, const double* scale,
+                       const int32_t* cat, int ncat, double* var, double* preds, double* cat_sum, double* cat_max,
+                       int64_t* cat_count);
+
+/* Same with device outputs (d_var, d_preds: m doubles; d_cat_sum, d_cat_max: ncat doubles; d_cat_count: ncat int64) and a
+ * device d_scale, queued on the context's stream; M, beta and cat stay host arrays.  Returns once the work is queued. */
+int fsnap_row_variance_device(fsnap_ctx* ctx, int mode, int64_t K, int64_t J, const double* M, const double* beta,
+                              const double* d_scale, const int32_t* cat, int ncat, double* d_var, double* d_preds,
+                              double* d_cat_sum, double* d_cat_max, int64_t* d_cat_count);
+
 /* ---- K x K solve (host side, no context needed) ----------------------------------- */
 
 /* Solve the K x K system given the statistics.  `kind` is one of FSNAP_SOLVE_*;
