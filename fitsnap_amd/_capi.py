@@ -66,6 +66,7 @@ SIGNATURES = {
     "fsnap_residual_rhs": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_double)]),
     "fsnap_merr_eval": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_double, POINTER(c_double), c_void_p,
                                 c_void_p]),
+    "fsnap_sse_batch": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, POINTER(c_int64)]),
     "fsnap_solve": (c_int, [c_int, c_double, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_double)]),
     "fsnap_cond_info": (c_int, [c_void_p]),
     "fsnap_lasso_gram": (c_int, [c_int64, c_void_p, c_void_p, c_double, c_double, c_int64, c_double, c_void_p,
@@ -639,6 +640,22 @@ class HipContext:
         h = np.empty(self.K)
         self._check(self._lib.fsnap_merr_eval(self._h, code, self.K, _ptr(c), _ptr(q), float(d), byref(val), _ptr(g), _ptr(h)))
         return val.value, g, h
+
+    SSE_MAX_P = 16
+
+    def sse_batch(self, U):
+        """Weighted residual sums of P <= 16 coefficient vectors (rows of U, P x K) over the resident training rows
+        (``fsnap_sse_batch``): returns (sse[P], n_train) with sse[p] = sum (w (a . u_p - b))^2.  sse[p] depends on
+        u_p and the rows only, whatever else is in the batch."""
+        U = np.ascontiguousarray(U, dtype=np.float64)
+        if U.ndim == 1:
+            U = U.reshape(1, -1)
+        if U.ndim != 2 or not 1 <= U.shape[0] <= self.SSE_MAX_P:
+            raise ValueError(f"U has shape {U.shape}, expected (P, K) with 1 <= P <= {self.SSE_MAX_P}")
+        sse = np.empty(U.shape[0])
+        n = c_int64(0)
+        self._check(self._lib.fsnap_sse_batch(self._h, U.shape[1], _ptr(U), U.shape[0], _ptr(sse), byref(n)))
+        return sse, int(n.value)
 
     def normal_eq_accumulate(self, d_packed_ptr: int):
         """d_packed (device) += statistics of the resident rows (streaming / transpose-trick accumulation)."""

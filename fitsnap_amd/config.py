@@ -6,7 +6,8 @@ input is either a dict of dicts (library mode, input.py:141-151) or an INI file 
 with configparser (input.py:110-140).  Only keys the hot path needs are typed and
 defaulted here, with the reference's defaults:
 
-  [SOLVER] solver=SVD, compute_testerrs, detailed_errors, nsam, cov_nugget,
+  [SOLVER] solver=SVD, compute_testerrs, detailed_errors, nsam (133 for solver=MCMC, else 0), cov_nugget,
+           mcmc_num=10000, mcmc_gamma=0.01, mcmc_sigma=0.1,
            merr_mult=0, merr_method=abc, merr_cfs=all       (solver_sections/solver.py:15-35)
   [RIDGE]  alpha=1.0E-8, local_solver=0                     (solver_sections/ridge.py:13-14)
   [ARD]    alphabig, alphasmall, lambdabig, lambdasmall, threshold_lambda, directmethod,
@@ -162,7 +163,12 @@ class Config:
             name="SOLVER", solver=solver,
             compute_testerrs=_get(sol, "compute_testerrs", "0", "bool"),
             detailed_errors=_get(sol, "detailed_errors", "0", "bool"),
-            nsam=_get(sol, "nsam", "0", "int"), cov_nugget=_get(sol, "cov_nugget", "0.0", "float"),
+            # nsam defaults to 133 for MCMC only; the comparison is case-sensitive, as the reference's (solver.py:25-28)
+            nsam=_get(sol, "nsam", "133" if solver == "MCMC" else "0", "int"),
+            cov_nugget=_get(sol, "cov_nugget", "0.0", "float"),
+            # MCMC (solver_sections/solver.py:30-32)
+            mcmc_num=_get(sol, "mcmc_num", "10000", "int"), mcmc_gamma=_get(sol, "mcmc_gamma", "0.01", "float"),
+            mcmc_sigma=_get(sol, "mcmc_sigma", "0.1", "float"),
             # MERR (solver_sections/solver.py:33-35)
             merr_mult=_get(sol, "merr_mult", "0", "bool"), merr_method=_get(sol, "merr_method", "abc", "str"),
             merr_cfs=_get(sol, "merr_cfs", "all", "str"),

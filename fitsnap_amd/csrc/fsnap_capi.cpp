@@ -1910,6 +1910,46 @@ int fsnap_merr_eval(fsnap_ctx* ctx, int method, int64_t K, const double* c, cons
     return FSNAP_OK;
 }
 
+int fsnap_sse_batch(fsnap_ctx* ctx, int64_t K, const double* U, int P, double* sse, int64_t* n_train) {
+    if (!ctx) return FSNAP_E_ARG;
+    if (!U || !sse) return ctx->fail(FSNAP_E_ARG, "fsnap_sse_batch: NULL argument");
+    if (P < 1 || P > fsnap::SSE_MAX_P)
+        return ctx->fail(FSNAP_E_ARG, "fsnap_sse_batch: P = %d, expected 1 ... %d", P, fsnap::SSE_MAX_P);
+    if (K < 1 || K > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "fsnap_sse_batch: K = %lld", (long long)K);
+    if (ctx->m <= 0) {                   // no rows on this context (a rank without rows): nothing to add
+        for (int p = 0; p < P; ++p) sse[p] = 0.0;
+        if (n_train) *n_train = 0;
+        return FSNAP_OK;
+    }
+    int rc;
+    if ((rc = check_rows(ctx)) || (rc = check_weights(ctx))) return rc;
+    if (K != ctx->K) return ctx->fail(FSNAP_E_ARG, "fsnap_sse_batch: K = %lld, the resident rows have %lld columns",
+                                      (long long)K, (long long)ctx->K);
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    const int nb = fsnap::sse_num_blocks(ctx->m);
+    const size_t ncol = fsnap::SSE_MAX_P + 1;
+    const size_t nup = (size_t)4 * ((K + 15) / 16) * 64;
+    if (!ctx->sse_U.ensure(nup * 8) || !ctx->sse_part.ensure((size_t)nb * ncol * 8) || !ctx->sse_out.ensure(ncol * 8))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(sse) failed");
+    const unsigned char* mask = ctx->dmask;
+    if (!mask) {
+        if ((rc = ensure_ones(ctx))) return rc;
+        mask = (const unsigned char*)ctx->ones.p;
+    }
+    ctx->sse_hU.resize(nup);
+    fsnap::sse_pack_u(U, P, (int)K, ctx->sse_hU.data());
+    FSNAP_HIP(hipMemcpyAsync(ctx->sse_U.p, ctx->sse_hU.data(), nup * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(U)");
+    FSNAP_HIP(fsnap::launch_sse_batch(ctx->dA, ctx->lda, ctx->m, (int)K, (const double*)ctx->sse_U.p, ctx->db, ctx->dw, mask,
+                                      (double*)ctx->sse_part.p, (double*)ctx->sse_out.p, ctx->stream),
+              "launch fsnap_sse_rows_k");
+    double out[fsnap::SSE_MAX_P + 1];
+    FSNAP_HIP(hipMemcpyAsync(out, ctx->sse_out.p, ncol * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(sse)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    for (int p = 0; p < P; ++p) sse[p] = out[p];
+    if (n_train) *n_train = (int64_t)out[fsnap::SSE_MAX_P];
+    return FSNAP_OK;
+}
+
 int fsnap_timing(fsnap_ctx* ctx, double* ms, int n) {
     if (!ctx || !ms || n < 0 || n > 8) return FSNAP_E_ARG;
     FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");

@@ -105,6 +105,8 @@ struct fsnap_ctx {
     DevBuf du, dspart, dsvec;                     // refinement: row weights u, per-workgroup partials, s
     DevBuf merr_cq, merr_part, merr_out;          // fsnap_merr_eval: [c | q], partials [g | h | val] per workgroup, sums
     DevBuf merr_u, merr_vpart;                    // ... K > 288: per-row (alpha w, beta w^2), per-workgroup values
+    DevBuf sse_U, sse_part, sse_out;              // fsnap_sse_batch: packed vectors, partials [sse | n] per workgroup, sums
+    std::vector<double> sse_hU;                   // host staging of the packed vectors (kept until the copy is done)
     // batched candidate fits (fsnap_cat_prepare ... fsnap_candidate_rows, kernels of fsnap_cand.hip): row ids sorted by
     // category and chunk lists of the training rows (_t) and of all categorised rows (_a), the base weights w0 as they were at
     // prepare time, the per-category statistics and the candidates' packed statistics

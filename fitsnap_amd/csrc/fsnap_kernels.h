@@ -151,6 +151,15 @@ hipError_t launch_merr(const double* A, int64_t lda, const double* cq, int64_t m
                        const unsigned char* mask, int method, double d, double* u, double* val_part, double* partial,
                        double* out, hipStream_t st);
 
+// Weighted residual sums of up to SSE_MAX_P coefficient vectors (fsnap_mcmc.hip, kernels S1 / S1G).  Up: the vectors packed by
+// sse_pack_u (host) into the MFMA operand order, 4 ceil(K / 16) x 64 doubles, on the device.  out[SSE_MAX_P + 1] =
+// [sse_0 .. sse_15 | n] (slots past P are zero).  Scratch: partial[sse_num_blocks(m)][SSE_MAX_P + 1].  m >= 1.
+constexpr int SSE_MAX_P = 16;
+int sse_num_blocks(int64_t m);
+void sse_pack_u(const double* U, int P, int K, double* Up);
+hipError_t launch_sse_batch(const double* A, int64_t lda, int64_t m, int K, const double* Up, const double* b, const double* w,
+                            const unsigned char* mask, double* partial, double* out, hipStream_t st);
+
 // Batched candidate fits (fsnap_cand.hip).  Rows are gathered through an index sorted by category and cut into chunks of
 // at most CAT_CHUNK_ROWS rows of one category; every chunk has at least one row.
 struct CatChunk {

@@ -7,5 +7,6 @@ from .ard import ARD  # noqa: F401
 from .anl import ANL  # noqa: F401
 from .lasso import LASSO  # noqa: F401
 from .merr import MERR  # noqa: F401
+from .mcmc import MCMC  # noqa: F401
 from .candidates import CandidateFits  # noqa: F401
 from .solver_factory import solver, search  # noqa: F401

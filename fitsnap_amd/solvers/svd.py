@@ -10,6 +10,28 @@ from .._hostblas import blas_threads
 from .solver import Solver
 
 
+def rows_lstsq(solver, a=None, b=None, w=None, fs_dict=None, trainall=False, rcond=1.0e-13):
+    """``lstsq(aw, bw, rcond)`` of the rows (svd.py:54), the path of ``SVD.perform_fit`` without the transpose trick; also
+    the start of the MCMC chain (mcmc.py:122).  ``solver`` provides the engine (rows, weights, statistics) and its
+    ``refine_steps`` / ``row_space`` settings.  Collective; returns the coefficients (every rank computes them)."""
+    pt = solver.pt
+    solver.last_row_space = None
+    # PROBE: a system the Cholesky factorisations cannot resolve comes back at once (rank -1) instead of going
+    # through the library's eigen-truncation of G -- that answer would be discarded for the row-space solve anyway,
+    # and at K = 1595 the Jacobi sweeps behind it take a minute
+    fit = solver._fit_and_solve(_capi.SOLVE_LSTSQ_PROBE, rcond, a, b, w, fs_dict, trainall)
+    K = len(fit)
+    on_gpu = (pt.comm_kind != "torch" or not pt.multi) and (solver._rows_on_device() or pt.multi)
+    if solver.row_space and on_gpu and solver._needs_row_space(K):
+        # ill-conditioned or rank deficient: lstsq's answer lives in the rows, not in the K x K statistics
+        fit = solver._row_space_fit(K, rcond)
+    else:
+        fit = solver._resolve_probe(_capi.SOLVE_LSTSQ_PROBE, rcond, fit)
+        if solver.refine_steps and solver.last_rank == K:
+            fit = solver._refine(fit, _capi.SOLVE_LSTSQ, rcond, solver.refine_steps)
+    return fit
+
+
 class SVD(Solver):
     """``perform_fit`` = reference semantics of ``lstsq(aw, bw, 1.0e-13)`` (svd.py:54).
 
@@ -40,20 +62,7 @@ class SVD(Solver):
         pt = self.pt
         # every rank contributes its rows' statistics; the coefficients are published on rank 0 (svd.py:33)
         if not ("EXTRAS" in self.config.sections and self.config.sections["EXTRAS"].apply_transpose):
-            self.last_row_space = None
-            # PROBE: a system the Cholesky factorisations cannot resolve comes back at once (rank -1) instead of going
-            # through the library's eigen-truncation of G -- that answer would be discarded for the row-space solve anyway,
-            # and at K = 1595 the Jacobi sweeps behind it take a minute
-            fit = self._fit_and_solve(_capi.SOLVE_LSTSQ_PROBE, self.RCOND, a, b, w, fs_dict, trainall)
-            K = len(fit)
-            on_gpu = (pt.comm_kind != "torch" or not pt.multi) and (self._rows_on_device() or pt.multi)
-            if self.row_space and on_gpu and self._needs_row_space(K):
-                # ill-conditioned or rank deficient: lstsq's answer lives in the rows, not in the K x K statistics
-                fit = self._row_space_fit(K, self.RCOND)
-            else:
-                fit = self._resolve_probe(_capi.SOLVE_LSTSQ_PROBE, self.RCOND, fit)
-                if self.refine_steps and self.last_rank == K:
-                    fit = self._refine(fit, _capi.SOLVE_LSTSQ, self.RCOND, self.refine_steps)
+            fit = rows_lstsq(self, a, b, w, fs_dict, trainall, self.RCOND)
             if pt._rank == 0:
                 self.fit = fit
             return

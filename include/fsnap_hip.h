@@ -274,6 +274,16 @@ int fsnap_residual_rhs(fsnap_ctx* ctx, const double* beta, double* s, double* ss
 int fsnap_merr_eval(fsnap_ctx* ctx, int method, int64_t K, const double* c, const double* q, double d, double* val,
                     double* g, double* h);
 
+/* Weighted residual sums of P coefficient vectors over the resident training rows, one pass over A (the log-posterior of
+ * the MCMC solver, fitsnap3lib/solvers/mcmc.py logpost, for a batch of proposals; kernels S1 / S1G of csrc/fsnap_mcmc.hip,
+ * fp64 MFMA).  U: host, P x K row-major, 1 <= P <= 16.  Over the rows of the current mask (weight zero included):
+ *   sse[p] = sum_i (w_i (a_i . u_p - b_i))^2,   *n_train = number of rows in the mask   (n_train may be NULL)
+ * K must equal the resident rows' width, else FSNAP_E_ARG; P outside 1 ... 16: FSNAP_E_ARG.  With no rows (m = 0) the
+ * sums and the count are zero.  sse[p] depends only on u_p and the rows: bit-identical in any slot, for any P, whatever
+ * the other vectors, and run to run.  Test rows are dropped by selects (NaN / Inf in them reach nothing).  No atomics.
+ * The rows, weights and any category layout are left as they are.  Host in and out, synchronous. */
+int fsnap_sse_batch(fsnap_ctx* ctx, int64_t K, const double* U, int P, double* sse, int64_t* n_train);
+
 /* Predictive variance of the resident rows under a posterior covariance (Solver._compute_stdev, solver.py:440-472; the
  * ranking pass of the Bayesian active-learning loop, bayesian_active_learning.py:826-828), one pass over the rows (kernels
  * U1 / U1G of csrc/fsnap_uq.hip, fp64 MFMA).  M (host, K x J row-major) is copied to the device on every call; per row a_i:
