@@ -119,6 +119,8 @@ SIGNATURES = {
                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "fsnap_row_variance_device": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fsnap_loco_rows": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                c_void_p]),
 }
 
 _lib = None
@@ -824,6 +826,33 @@ class HipContext:
         self._check(self._lib.fsnap_row_variance_device(self._h, int(mode), K, J, _ptr(M), _ptr(beta), v(d_scale), _ptr(cat),
                                                         int(ncat), v(d_var), v(d_preds), v(d_cat_sum), v(d_cat_max),
                                                         v(d_cat_count)))
+
+    def loco_rows(self, M, beta, sorted_rows, cfg_offsets):
+        """Leave-one-configuration-out predictions of the resident training rows (``fsnap_loco_rows``): M (K x J) with
+        C = M M^T, the fit ``beta`` (K), the rows of configuration c at ``sorted_rows[cfg_offsets[c]:cfg_offsets[c + 1]]``.
+        Returns (pred (m, NaN where a row is not listed or its configuration is not identifiable), info (ncfg x 4:
+        d_c, smallest pivot, identifiable, n space))."""
+        M = _f64(M, "M")
+        if M.ndim == 1:
+            M = M.reshape(-1, 1)
+        if M.ndim != 2:
+            raise ValueError("M must be 2-D")
+        K, J = M.shape
+        beta = _f64(beta, "beta").reshape(-1)
+        if beta.shape != (K,):
+            raise ValueError(f"beta has shape {beta.shape}, expected ({K},)")
+        rows = np.ascontiguousarray(sorted_rows, dtype=np.int32).reshape(-1)
+        off = np.ascontiguousarray(cfg_offsets, dtype=np.int64).reshape(-1)
+        if off.size < 1:
+            raise ValueError("cfg_offsets needs ncfg + 1 entries")
+        ncfg = off.size - 1
+        if off[-1] != rows.size:
+            raise ValueError(f"cfg_offsets ends at {off[-1]}, sorted_rows has {rows.size} entries")
+        pred = np.empty(self.m)
+        info = np.empty((ncfg, 4))
+        self._check(self._lib.fsnap_loco_rows(self._h, K, J, _ptr(M), _ptr(beta), _ptr(rows) if rows.size else None,
+                                              _ptr(off), ncfg, _ptr(pred), _ptr(info)))
+        return pred, info
 
     def lstsq_rows(self, rcond: float, K: int = None):
         """``lstsq(aw, bw, rcond)`` of the resident rows computed on the rows (fsnap_lstsq_rows); collective when the

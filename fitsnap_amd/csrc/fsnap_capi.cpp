@@ -2478,3 +2478,123 @@ int fsnap_row_variance_device(fsnap_ctx* ctx, int mode, int64_t K, int64_t J, co
                               double* d_cat_sum, double* d_cat_max, int64_t* d_cat_count) {
     return row_variance(ctx, mode, K, J, M, beta, d_scale, cat, ncat, d_var, d_preds, d_cat_sum, d_cat_max, d_cat_count, true);
 }
+
+// ---- leave-one-configuration-out predictions of the resident training rows (kernels L1, L2 of fsnap_loco.hip) --------
+
+int fsnap_loco_rows(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, const double* beta, const int32_t* sorted_rows,
+                    const int64_t* cfg_offsets, int64_t ncfg, double* pred_out, double* cfg_info_out) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_loco_rows";
+    if (!M || !beta || !cfg_offsets || !pred_out || (ncfg > 0 && !cfg_info_out))
+        return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
+    if (K < 1 || K > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: K = %lld", who, (long long)K);
+    if (J < 1 || J > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: J = %lld", who, (long long)J);
+    if (ncfg < 0 || ncfg > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: ncfg = %lld", who, (long long)ncfg);
+    const int64_t m = ctx->m;
+    if (m > 0 && K != ctx->K)
+        return ctx->fail(FSNAP_E_ARG, "%s: K = %lld, the resident rows have %lld columns", who, (long long)K, (long long)ctx->K);
+    if (m > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: needs m < 2^31", who);
+    if (cfg_offsets[0] != 0) return ctx->fail(FSNAP_E_ARG, "%s: cfg_offsets[0] = %lld", who, (long long)cfg_offsets[0]);
+    for (int64_t c = 0; c < ncfg; ++c)
+        if (cfg_offsets[c + 1] < cfg_offsets[c])
+            return ctx->fail(FSNAP_E_ARG, "%s: cfg_offsets decrease at %lld", who, (long long)c);
+    const int64_t npos = cfg_offsets[ncfg];
+    if (npos > m) return ctx->fail(FSNAP_E_ARG, "%s: %lld positions for %lld rows", who, (long long)npos, (long long)m);
+    if (npos > 0 && !sorted_rows) return ctx->fail(FSNAP_E_ARG, "%s: sorted_rows is NULL", who);
+    {   // every position names a distinct row of the context: a row written by two configurations would be a race
+        std::vector<unsigned char> seen((size_t)std::max<int64_t>(m, 1), 0);
+        for (int64_t p = 0; p < npos; ++p) {
+            const int32_t r = sorted_rows[p];
+            if (r < 0 || r >= m || seen[(size_t)r])
+                return ctx->fail(FSNAP_E_ARG, "%s: sorted_rows[%lld] = %d is out of range or repeated", who, (long long)p, r);
+            seen[(size_t)r] = 1;
+        }
+    }
+    for (int64_t i = 0; i < m; ++i) pred_out[i] = std::numeric_limits<double>::quiet_NaN();
+    for (int64_t c = 0; c < ncfg; ++c) {      // empty configurations: nothing to leave out
+        cfg_info_out[4 * c] = 0.0;
+        cfg_info_out[4 * c + 1] = std::numeric_limits<double>::infinity();
+        cfg_info_out[4 * c + 2] = 1.0;
+        cfg_info_out[4 * c + 3] = 1.0;
+    }
+    if (npos == 0) return FSNAP_OK;
+    int rc;
+    if ((rc = check_rows(ctx)) || (rc = check_weights(ctx))) return rc;
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    if (ctx->uq_inflight) {
+        FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+        ctx->uq_inflight = false;
+    }
+    int npk = 0;
+    if ((rc = ensure_wpack(ctx, &npk))) return rc;
+    const double* wpack = ctx->wpack_override ? ctx->wpack_override : (const double*)ctx->wpack.p;
+    // configurations by solve size d_c = min(n_c, J): LDS kernels for d <= 32 / 64 / 128, global scratch beyond
+    const int Dbin[4] = {32, 64, fsnap::LOCO_MAX_LDS_D, 0};
+    std::vector<int32_t> lists[4];
+    int64_t dmax = 0;
+    for (int64_t c = 0; c < ncfg; ++c) {
+        const int64_t n = cfg_offsets[c + 1] - cfg_offsets[c];
+        if (n == 0) continue;
+        const int64_t d = std::min(n, J);
+        const int b = d <= 32 ? 0 : d <= 64 ? 1 : d <= fsnap::LOCO_MAX_LDS_D ? 2 : 3;
+        lists[b].push_back((int32_t)c);
+        if (b == 3) dmax = std::max(dmax, d);
+    }
+    const int64_t Kp = (K + 15) / 16 * 16, Jp = (J + 15) / 16 * 16;
+    const size_t nM = (size_t)(Kp * Jp);
+    ctx->loco_hM.assign(nM + (size_t)Kp, 0.0);
+    for (int64_t k = 0; k < K; ++k) std::memcpy(&ctx->loco_hM[(size_t)(k * Jp)], M + k * J, (size_t)J * 8);
+    std::memcpy(&ctx->loco_hM[nM], beta, (size_t)K * 8);
+    ctx->loco_hlist.clear();
+    for (auto& l : lists) ctx->loco_hlist.insert(ctx->loco_hlist.end(), l.begin(), l.end());
+    const int nblk_lds = std::max(1, 16 * ctx->num_cu);
+    int nblk[4];
+    for (int b = 0; b < 3; ++b) nblk[b] = (int)std::min<int64_t>((int64_t)lists[b].size(), nblk_lds);
+    // general path: one (dmax^2 + dmax) slice per workgroup, at most ~1 GiB of scratch and two workgroups per CU
+    const int64_t hslice = dmax * dmax + dmax;
+    nblk[3] = lists[3].empty() ? 0
+                               : (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)lists[3].size(), 2 * (int64_t)ctx->num_cu,
+                                                                              (int64_t)(1 << 27) / std::max<int64_t>(hslice, 1)}));
+    const int nvg = std::max({nblk[0], nblk[1], nblk[2], nblk[3], 1});
+    if (!ctx->loco_M.ensure((nM + (size_t)Kp) * 8) || !ctx->loco_idx.ensure((size_t)npos * 4) ||
+        !ctx->loco_off.ensure((size_t)(ncfg + 1) * 8) || !ctx->loco_list.ensure(std::max<size_t>(ctx->loco_hlist.size(), 1) * 4) ||
+        !ctx->loco_Z.ensure((size_t)npos * (size_t)Jp * 8) || !ctx->loco_aux.ensure((size_t)npos * 3 * 8) ||
+        !ctx->loco_pred.ensure((size_t)m * 8) || !ctx->loco_info.ensure((size_t)ncfg * 4 * 8) ||
+        !ctx->loco_v.ensure((size_t)nvg * (size_t)Jp * 8) || (nblk[3] > 0 && !ctx->loco_H.ensure((size_t)nblk[3] * (size_t)hslice * 8)))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(loco) failed");
+    FSNAP_HIP(hipMemcpyAsync(ctx->loco_M.p, ctx->loco_hM.data(), (nM + (size_t)Kp) * 8, hipMemcpyHostToDevice, ctx->stream),
+              "hipMemcpy(M)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->loco_idx.p, sorted_rows, (size_t)npos * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(idx)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->loco_off.p, cfg_offsets, (size_t)(ncfg + 1) * 8, hipMemcpyHostToDevice, ctx->stream),
+              "hipMemcpy(offsets)");
+    if (!ctx->loco_hlist.empty())
+        FSNAP_HIP(hipMemcpyAsync(ctx->loco_list.p, ctx->loco_hlist.data(), ctx->loco_hlist.size() * 4, hipMemcpyHostToDevice,
+                                 ctx->stream),
+                  "hipMemcpy(lists)");
+    FSNAP_HIP(hipMemsetAsync(ctx->loco_pred.p, 0xFF, (size_t)m * 8, ctx->stream), "hipMemset(pred)");   // all-ones: NaN
+    double* aux = (double*)ctx->loco_aux.p;
+    FSNAP_HIP(fsnap::launch_loco_zeta(ctx->dA, ctx->lda, (int)K, (const int*)ctx->loco_idx.p, npos, wpack,
+                                      (const double*)ctx->loco_M.p, (int)Jp, (const double*)ctx->loco_M.p + nM,
+                                      (double*)ctx->loco_Z.p, aux, aux + npos, aux + 2 * npos, ctx->stream),
+              "launch fsnap_loco_zeta_k");
+    size_t first = 0;
+    for (int b = 0; b < 4; ++b) {
+        const int ncl = (int)lists[b].size();
+        if (ncl > 0)
+            FSNAP_HIP(fsnap::launch_loco_cfg(Dbin[b], nblk[b], (const double*)ctx->loco_Z.p, (int)Jp, (int)J, aux, aux + npos,
+                                             aux + 2 * npos, (const int*)ctx->loco_idx.p, (const int64_t*)ctx->loco_off.p,
+                                             (const int*)ctx->loco_list.p + first, ncl, (double*)ctx->loco_H.p, (int)dmax,
+                                             (double*)ctx->loco_v.p, (double*)ctx->loco_pred.p, (double*)ctx->loco_info.p,
+                                             ctx->stream),
+                      "launch fsnap_loco_cfg_k");
+        first += (size_t)ncl;
+    }
+    ctx->loco_hinfo.resize((size_t)ncfg * 4);
+    FSNAP_HIP(hipMemcpyAsync(pred_out, ctx->loco_pred.p, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(pred)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->loco_hinfo.data(), ctx->loco_info.p, (size_t)ncfg * 32, hipMemcpyDeviceToHost, ctx->stream),
+              "hipMemcpy(info)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    for (int64_t c = 0; c < ncfg; ++c)
+        if (cfg_offsets[c + 1] > cfg_offsets[c]) std::memcpy(cfg_info_out + 4 * c, &ctx->loco_hinfo[(size_t)(4 * c)], 32);
+    return FSNAP_OK;
+}

@@ -124,6 +124,12 @@ struct fsnap_ctx {
     std::vector<int32_t> uq_hidx, uq_hcbeg;
     std::vector<int64_t> uq_hch, uq_hcount;
     bool uq_inflight = false;                     // copies out of the staging above may still be running
+    // fsnap_loco_rows: [padded M | padded beta], sorted row index, configuration offsets and per-bin lists, zeta per position
+    // (npos x Jp), (w, e, a . beta) per position, per-row predictions, per-configuration info, per-workgroup scratch (v; H of
+    // the configurations too large for LDS); kept between calls like the other workspaces
+    DevBuf loco_M, loco_idx, loco_off, loco_list, loco_Z, loco_aux, loco_pred, loco_info, loco_v, loco_H;
+    std::vector<double> loco_hM, loco_hinfo;
+    std::vector<int32_t> loco_hlist;
     double* pinned = nullptr;                     // page-locked host staging of the packed statistics: plain (coarse-grained)
                                                   // pinned memory, the target of DMA copies only -- copies into COHERENT
                                                   // host memory were bimodal (2 MB in 0.05 or in 8 ms)

@@ -205,6 +205,22 @@ hipError_t launch_uq_rows(int mode, const double* A, int64_t lda, int64_t m, int
 hipError_t launch_uq_cat(const double* var, const double* scale, const int* idx, const CatChunk* chunks, int64_t nchunks,
                          const int* cbeg, int ncat, double* part, double* cat_sum, double* cat_max, hipStream_t st);
 
+// Leave-one-configuration-out predictions (fsnap_loco.hip).  Kernel L1: for the npos positions of the sorted row index idx,
+// Z[p] = a_idx[p] M (Jp doubles per position; Mp: device, Kp x Jp row-major, zero-padded as for launch_uq_rows), pb[p] =
+// a . beta (bp: Kp doubles), pw[p] = w_eff, pe[p] = w_eff b - w_eff (a . beta) from wpack (kernel 1A's pairs).
+hipError_t launch_loco_zeta(const double* A, int64_t lda, int K, const int* idx, int64_t npos, const double* wpack,
+                            const double* Mp, int Jp, const double* bp, double* Z, double* pw, double* pe, double* pb,
+                            hipStream_t st);
+// Kernel L2 over the configurations clist[ncl] (positions off[c] .. off[c + 1]); D = 32 / 64 / 128: d_c = min(n_c, J) <= D,
+// H in LDS; D = 0: any d_c <= dmax, H in Hg (nblocks x (dmax^2 + dmax) doubles).  vg: nblocks x Jp doubles of scratch.
+// pred[idx[p]] = LOO prediction (NaN for a configuration that is not identifiable); info[4 c ..] = (d_c, smallest pivot,
+// identifiable, n space).
+constexpr int LOCO_MAX_LDS_D = 128;
+constexpr double LOCO_PIVOT_TOL = 1e-10;     // pivots of I - S_c (diagonal <= 1) at or below this: not identifiable
+hipError_t launch_loco_cfg(int D, int nblocks, const double* Z, int Jp, int J, const double* pw, const double* pe,
+                           const double* pb, const int* idx, const int64_t* off, const int* clist, int ncl, double* Hg,
+                           int dmax, double* vg, double* pred, double* info, hipStream_t st);
+
 // Row-space solve (fsnap_trsm.hip).  Q <- X R^-1 by blocked substitution over the columns, one wave per 64 rows:
 // first pass X = diag(w_eff) A (src = A, leading dimension lds, per-row pairs wpack = (w_eff, w_eff b); rows with
 // w_eff = 0 become zero rows), later passes X = Q in place (src = Q, wpack = nullptr).  R: device, K16 x K16 row-major

@@ -25,7 +25,7 @@ import numpy as np
 
 from .. import _capi
 from .._hostblas import blas_threads
-from . import uq
+from . import loco, uq
 
 
 class _TrainWeights:
@@ -1078,3 +1078,21 @@ class Solver:
             with np.errstate(invalid="ignore", divide="ignore"):
                 res["cat_mean"] = res["cat_sum"] / res["cat_count"]
         return res
+
+    # ------------------------------------------------------------------------------
+    # leave-one-configuration-out errors (solvers/loco.py, csrc/fsnap_loco.hip)
+    # ------------------------------------------------------------------------------
+    def loco_errors(self, by="Configs", fs_dict=None, b=None, w=None):
+        """Exact leave-one-unit-out errors of the last fit without refits (SVD, RIDGE, ANL): every training row is
+        predicted by the fit without the rows of its unit, the label ``fs_dict[by]`` of the row (``by="Configs"``:
+        leave-one-configuration-out, ``by="Groups"``: leave-one-group-out), on the GPU from the resident training rows.
+
+        ``fs_dict=None`` takes the labels of ``pt.fitsnap_dict`` (``pt.local_lists`` on several ranks) and the shared
+        ``b`` / ``w``; an explicit ``fs_dict`` needs the truths ``b`` and weights ``w`` of the fit (one per row or one per
+        training row).  Collective on several ranks; every unit must live on one rank.  Returns ``LocoResult(errors,
+        preds, units, unidentifiable)``: ``errors`` in the layout of ``error_analysis`` over the training rows (rank 0;
+        None elsewhere), the per-row LOO predictions of this rank's rows (NaN on testing rows and on the rows of units
+        that are not identifiable without themselves), a per-unit DataFrame (label, group, rows, weighted LOO SSE,
+        max |LOO residual|, identifiable, d, smallest pivot) and the number of units that are not identifiable.
+        Raises ValueError for solvers whose fit is not a linear smoother of the rows and for ``apply_transpose``."""
+        return loco.loco_errors(self, by, fs_dict, b, w)

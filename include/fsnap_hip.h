@@ -310,6 +310,22 @@ int fsnap_row_variance_device(fsnap_ctx* ctx, int mode, int64_t K, int64_t J, co
                               const double* d_scale, const int32_t* cat, int ncat, double* d_var, double* d_preds,
                               double* d_cat_sum, double* d_cat_max, int64_t* d_cat_count);
 
+/* Exact leave-one-configuration-out (LOCO) predictions of a linear smoother from the resident training rows (kernels L1, L2 of
+ * csrc/fsnap_loco.hip, fp64 MFMA; no refit).  M (host, K x J row-major) is any factor of C = (G + alpha I)^-1 = M M^T of the
+ * fit (RIDGE: its alpha; ANL: pinv with cov_nugget; SVD: alpha = 0, or V_r Lambda_r^-1/2 of the kept directions), beta
+ * (host, K) the fit.  sorted_rows[cfg_offsets[ncfg]] (host, int32) lists the rows of configuration c at positions
+ * cfg_offsets[c] ... cfg_offsets[c + 1] - 1 (host, int64, cfg_offsets[0] = 0, non-decreasing; every row at most once).
+ * With zeta_i = a_i M, z_i = w_i zeta_i, e_i = w_i b_i - w_i (a_i . beta) (w_i = 0 off the mask) and S_c = Z_c^T Z_c:
+ *     v_c = (I_J - S_c)^-1 Z_c^T e_c  (solved in J space, or in n space as Z_c^T (I_n - Z_c Z_c^T)^-1 e_c when n_c <= J)
+ *     pred_out[i] = a_i . beta - zeta_i . v_c = a_i . beta_{-c}     for every row i of c
+ * pred_out: m doubles (NaN for rows that are not listed, and for every row of a configuration that is not identifiable);
+ * cfg_info_out: ncfg x 4 doubles (d_c = min(n_c, J), smallest Cholesky pivot of I - S_c, identifiable 1 / 0, n space 1 / 0).
+ * A configuration is not identifiable when a pivot is <= 1e-10 (lambda_max(S_c) -> 1; it is never divided through).
+ * d_c <= 128 is solved in LDS, larger d_c through global scratch.  K must equal the resident rows' width.  A row's result is
+ * bit-identical run to run and under any permutation of the configurations; no atomics.  Host in and out, synchronous. */
+int fsnap_loco_rows(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, const double* beta, const int32_t* sorted_rows,
+                    const int64_t* cfg_offsets, int64_t ncfg, double* pred_out, double* cfg_info_out);
+
 /* ---- K x K solve (host side, no context needed) ----------------------------------- */
 
 /* Solve the K x K system given the statistics.  `kind` is one of FSNAP_SOLVE_*;
