@@ -30,6 +30,8 @@ REDUCE_SUM, REDUCE_MAX, REDUCE_MIN = 0, 1, 2
 MERR_IID, MERR_ABC, MERR_FULL = 0, 1, 2
 CAND_ERROR_SUMS, CAND_RHS = 0, 1            # fsnap_candidate_rows: what
 UQ_QUAD, UQ_NORM = 0, 1                     # fsnap_row_variance: mode
+SELECT_SUM, SELECT_MAX, SELECT_MEAN = 0, 1, 2   # fsnap_select_begin: objective
+SELECT_OBJECTIVES = {"sum": SELECT_SUM, "max": SELECT_MAX, "mean": SELECT_MEAN}
 MERR_METHODS = {"iid": MERR_IID, "abc": MERR_ABC, "full": MERR_FULL}
 
 _P_D = POINTER(c_double)
@@ -121,6 +123,12 @@ SIGNATURES = {
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fsnap_loco_rows": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                 c_void_p]),
+    "fsnap_select_begin": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int]),
+    "fsnap_select_pick": (c_int, [c_void_p, c_int, POINTER(ctypes.c_int32), POINTER(c_double)]),
+    "fsnap_select_retire": (c_int, [c_void_p, ctypes.c_int32]),
+    "fsnap_select_downdate": (c_int, [c_void_p, c_int64, c_int64, c_void_p]),
+    "fsnap_select_state": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fsnap_select_end": (c_int, [c_void_p]),
 }
 
 _lib = None
@@ -826,6 +834,64 @@ class HipContext:
         self._check(self._lib.fsnap_row_variance_device(self._h, int(mode), K, J, _ptr(M), _ptr(beta), v(d_scale), _ptr(cat),
                                                         int(ncat), v(d_var), v(d_preds), v(d_cat_sum), v(d_cat_max),
                                                         v(d_cat_count)))
+
+    # -- greedy batch selection (fsnap_select_*) ------------------------------------------
+    def select_begin(self, M, mode=UQ_QUAD, scale=None, cat=None, ncat=0, objective=SELECT_SUM):
+        """Start a selection session on the resident rows (``fsnap_select_begin``): the variances and category sums of
+        ``row_variance(M, mode, scale=, cat=, ncat=)`` stay on the device; ``objective`` is SELECT_SUM / _MAX / _MEAN."""
+        M = _f64(M, "M")
+        if M.ndim == 1:
+            M = M.reshape(-1, 1)
+        if M.ndim != 2:
+            raise ValueError("M must be 2-D")
+        K, J = M.shape
+        m = self.m
+        if scale is not None:
+            scale = _f64(scale, "scale").reshape(-1)
+            if scale.shape != (m,):
+                raise ValueError(f"scale has shape {scale.shape}, expected ({m},)")
+        if cat is None:
+            raise ValueError("select_begin needs categories")
+        cat = np.ascontiguousarray(cat, dtype=np.int32)
+        if cat.shape != (m,):
+            raise ValueError(f"cat has shape {cat.shape}, expected ({m},)")
+        self._check(self._lib.fsnap_select_begin(self._h, int(mode), K, J, _ptr(M), _ptr(scale), _ptr(cat) if m else None,
+                                                 int(ncat), int(objective)))
+        self._select_shape = (m, int(ncat))
+
+    def select_pick(self, retire=True):
+        """(category, score) of the best live category (``fsnap_select_pick``; category -1 when none is left); with
+        ``retire`` it leaves the session."""
+        c, s = ctypes.c_int32(-1), c_double(0.0)
+        self._check(self._lib.fsnap_select_pick(self._h, int(bool(retire)), byref(c), byref(s)))
+        return c.value, s.value
+
+    def select_retire(self, category):
+        """Take a live category out of the session (``fsnap_select_retire``)."""
+        self._check(self._lib.fsnap_select_retire(self._h, int(category)))
+
+    def select_downdate(self, V):
+        """var_i -= ||a_i V||^2 on the session's resident variances, then the live categories' scores again
+        (``fsnap_select_downdate``); V is K x J."""
+        V = _f64(V, "V")
+        if V.ndim == 1:
+            V = V.reshape(-1, 1)
+        if V.ndim != 2:
+            raise ValueError("V must be 2-D")
+        self._check(self._lib.fsnap_select_downdate(self._h, V.shape[0], V.shape[1], _ptr(V)))
+
+    def select_state(self, want_var=True):
+        """The session's state (``fsnap_select_state``): dict of "var", "cat_sum", "cat_max", "cat_count", "alive"."""
+        m, ncat = getattr(self, "_select_shape", (0, 0))
+        var = np.empty(m) if want_var else None
+        sums, maxs = np.empty(ncat), np.empty(ncat)
+        counts, alive = np.empty(ncat, dtype=np.int64), np.empty(ncat, dtype=np.int32)
+        self._check(self._lib.fsnap_select_state(self._h, _ptr(var), _ptr(sums), _ptr(maxs), _ptr(counts), _ptr(alive)))
+        return {"var": var, "cat_sum": sums, "cat_max": maxs, "cat_count": counts, "alive": alive.astype(bool)}
+
+    def select_end(self):
+        """Drop the selection session (``fsnap_select_end``)."""
+        self._check(self._lib.fsnap_select_end(self._h))
 
     def loco_rows(self, M, beta, sorted_rows, cfg_offsets):
         """Leave-one-configuration-out predictions of the resident training rows (``fsnap_loco_rows``): M (K x J) with

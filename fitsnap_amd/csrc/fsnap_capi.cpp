@@ -387,6 +387,7 @@ int staged_rows_h2d(fsnap_ctx* ctx, void* dst, const void* src, size_t rows, siz
 
 // the category layout of the candidate kernels belongs to the rows it was prepared for: any change of the resident rows drops it
 void cand_forget(fsnap_ctx* ctx) {
+    ctx->sel_active = false;          // a selection session (fsnap_select_*) belongs to the rows as well
     ctx->cand_layout = 0;
     ctx->cand_dA = nullptr;
     ctx->cand_stats_K = 0;
@@ -2477,6 +2478,164 @@ int fsnap_row_variance_device(fsnap_ctx* ctx, int mode, int64_t K, int64_t J, co
                               const double* d_scale, const int32_t* cat, int ncat, double* d_var, double* d_preds,
                               double* d_cat_sum, double* d_cat_max, int64_t* d_cat_count) {
     return row_variance(ctx, mode, K, J, M, beta, d_scale, cat, ncat, d_var, d_preds, d_cat_sum, d_cat_max, d_cat_count, true);
+}
+
+// ---- greedy batch selection on the resident rows (kernels B1 ... B4 of fsnap_select.hip) -----------------------------
+
+namespace {
+
+int select_session(fsnap_ctx* ctx, const char* who) {
+    if (!ctx->sel_active)
+        return ctx->fail(FSNAP_E_ARG, "%s: no selection session (fsnap_select_begin; new rows or a new category layout end one)",
+                         who);
+    return FSNAP_OK;
+}
+
+int select_refresh(fsnap_ctx* ctx) {
+    double* dcat = (double*)ctx->sel_cat.p;
+    FSNAP_HIP(fsnap::launch_sel_scores((const double*)ctx->sel_var.p, ctx->sel_has_scale ? (const double*)ctx->sel_scale.p : nullptr,
+                                       (const int*)ctx->sel_idx.p, (const fsnap::CatChunk*)ctx->sel_ch.p, ctx->sel_nch,
+                                       (const int*)ctx->sel_cbeg.p, (const int*)ctx->sel_alive.p, ctx->sel_ncat,
+                                       (double*)ctx->sel_part.p, dcat, dcat + ctx->sel_ncat, ctx->stream),
+              "launch fsnap_sel_chunk_k");
+    return FSNAP_OK;
+}
+
+}  // namespace
+
+int fsnap_select_begin(fsnap_ctx* ctx, int mode, int64_t K, int64_t J, const double* M, const double* scale, const int32_t* cat,
+                       int ncat, int objective) {
+    if (!ctx) return FSNAP_E_ARG;
+    ctx->sel_active = false;
+    if (objective != FSNAP_SELECT_SUM && objective != FSNAP_SELECT_MAX && objective != FSNAP_SELECT_MEAN)
+        return ctx->fail(FSNAP_E_ARG, "fsnap_select_begin: unknown objective %d", objective);
+    if (ncat <= 0 || (ctx->m > 0 && !cat)) return ctx->fail(FSNAP_E_ARG, "fsnap_select_begin: categories are needed (ncat = %d)", ncat);
+    if (!M) return ctx->fail(FSNAP_E_ARG, "fsnap_select_begin: M is NULL");
+    const int64_t m = ctx->m;
+    static const int32_t no_rows = -1;
+    if (!cat) cat = &no_rows;             // m = 0: never read
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    if (!ctx->sel_var.ensure((size_t)std::max<int64_t>(m, 1) * 8) || !ctx->sel_cat.ensure((size_t)ncat * 16) ||
+        !ctx->sel_count.ensure((size_t)ncat * 8) || !ctx->sel_alive.ensure((size_t)ncat * 4) || !ctx->sel_out.ensure(16) ||
+        (scale && !ctx->sel_scale.ensure((size_t)std::max<int64_t>(m, 1) * 8)))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(select) failed");
+    if (scale && m > 0)
+        FSNAP_HIP(hipMemcpyAsync(ctx->sel_scale.p, scale, (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(scale)");
+    // the initial variances and scores are those of fsnap_row_variance (kernels U1 / U1G, U2, U3), left on the device
+    double* dcat = (double*)ctx->sel_cat.p;
+    int rc = row_variance(ctx, mode, K, J, M, nullptr, scale && m > 0 ? (const double*)ctx->sel_scale.p : nullptr, cat, ncat,
+                          m > 0 ? (double*)ctx->sel_var.p : nullptr, nullptr, dcat, dcat + ncat, nullptr, true);
+    if (rc) return rc;
+    // the session's own copy of the category layout: a later fsnap_row_variance call may replace the context's
+    const int64_t nch = ctx->uq_hcbeg[(size_t)ncat];
+    if (!ctx->sel_idx.ensure((size_t)std::max<int64_t>(m, 1) * 4) || !ctx->sel_ch.ensure((size_t)std::max<int64_t>(nch, 1) * 16) ||
+        !ctx->sel_cbeg.ensure(((size_t)ncat + 1) * 4) || !ctx->sel_part.ensure((size_t)std::max<int64_t>(nch, 1) * 16))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(select categories) failed");
+    if (m > 0) FSNAP_HIP(hipMemcpyAsync(ctx->sel_idx.p, ctx->uq_idx.p, (size_t)m * 4, hipMemcpyDeviceToDevice, ctx->stream), "hipMemcpy(idx)");
+    if (nch > 0)
+        FSNAP_HIP(hipMemcpyAsync(ctx->sel_ch.p, ctx->uq_ch.p, (size_t)nch * 16, hipMemcpyDeviceToDevice, ctx->stream), "hipMemcpy(chunks)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->sel_cbeg.p, ctx->uq_cbeg.p, ((size_t)ncat + 1) * 4, hipMemcpyDeviceToDevice, ctx->stream),
+              "hipMemcpy(cbeg)");
+    ctx->sel_hcount = ctx->uq_hcount;
+    ctx->sel_halive.resize((size_t)ncat);
+    for (int c = 0; c < ncat; ++c) ctx->sel_halive[(size_t)c] = ctx->sel_hcount[(size_t)c] > 0;    // an empty category is never picked
+    FSNAP_HIP(hipMemcpyAsync(ctx->sel_count.p, ctx->sel_hcount.data(), (size_t)ncat * 8, hipMemcpyHostToDevice, ctx->stream),
+              "hipMemcpy(count)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->sel_alive.p, ctx->sel_halive.data(), (size_t)ncat * 4, hipMemcpyHostToDevice, ctx->stream),
+              "hipMemcpy(alive)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    ctx->uq_inflight = false;
+    ctx->sel_m = m;
+    ctx->sel_nch = m > 0 ? nch : 0;
+    ctx->sel_ncat = ncat;
+    ctx->sel_objective = objective;
+    ctx->sel_has_scale = scale && m > 0;
+    ctx->sel_active = true;
+    return FSNAP_OK;
+}
+
+int fsnap_select_pick(fsnap_ctx* ctx, int retire, int32_t* category, double* score) {
+    if (!ctx) return FSNAP_E_ARG;
+    int rc = select_session(ctx, "fsnap_select_pick");
+    if (rc) return rc;
+    if (!category || !score) return ctx->fail(FSNAP_E_ARG, "fsnap_select_pick: NULL argument");
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    const double* dcat = (const double*)ctx->sel_cat.p;
+    FSNAP_HIP(fsnap::launch_sel_pick(dcat, dcat + ctx->sel_ncat, (const int64_t*)ctx->sel_count.p, (int*)ctx->sel_alive.p,
+                                     ctx->sel_ncat, ctx->sel_objective, retire != 0, (double*)ctx->sel_out.p, ctx->stream),
+              "launch fsnap_sel_pick_k");
+    double out[2] = {0.0, -1.0};
+    FSNAP_HIP(hipMemcpyAsync(out, ctx->sel_out.p, 16, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(pick)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    const int32_t c = (int32_t)out[1];
+    if (c >= ctx->sel_ncat) return ctx->fail(FSNAP_E_HIP, "fsnap_select_pick: category %d out of range", c);
+    if (retire && c >= 0) ctx->sel_halive[(size_t)c] = 0;
+    *category = c < 0 ? -1 : c;
+    *score = out[0];
+    return FSNAP_OK;
+}
+
+int fsnap_select_retire(fsnap_ctx* ctx, int32_t category) {
+    if (!ctx) return FSNAP_E_ARG;
+    int rc = select_session(ctx, "fsnap_select_retire");
+    if (rc) return rc;
+    if (category < 0 || category >= ctx->sel_ncat || !ctx->sel_halive[(size_t)category])
+        return ctx->fail(FSNAP_E_ARG, "fsnap_select_retire: category %d is not alive", category);
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    FSNAP_HIP(hipMemsetAsync((int32_t*)ctx->sel_alive.p + category, 0, 4, ctx->stream), "hipMemset(alive)");
+    ctx->sel_halive[(size_t)category] = 0;
+    return FSNAP_OK;
+}
+
+int fsnap_select_downdate(fsnap_ctx* ctx, int64_t K, int64_t J, const double* V) {
+    if (!ctx) return FSNAP_E_ARG;
+    int rc = select_session(ctx, "fsnap_select_downdate");
+    if (rc) return rc;
+    if (!V) return ctx->fail(FSNAP_E_ARG, "fsnap_select_downdate: V is NULL");
+    if (K < 1 || K > 0x3FFFFFFF || J < 1 || J > 0x3FFFFFFF)
+        return ctx->fail(FSNAP_E_ARG, "fsnap_select_downdate: K = %lld, J = %lld", (long long)K, (long long)J);
+    const int64_t m = ctx->sel_m;
+    if (m == 0) return FSNAP_OK;
+    if (m != ctx->m || K != ctx->K)
+        return ctx->fail(FSNAP_E_ARG, "fsnap_select_downdate: K = %lld, the resident rows have %lld columns", (long long)K,
+                         (long long)ctx->K);
+    if ((rc = check_rows(ctx))) return rc;
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    const int64_t Kp = (K + 15) / 16 * 16, Jp = (J + 15) / 16 * 16;
+    const size_t nV = (size_t)(Kp * Jp);
+    ctx->sel_hV.assign(nV, 0.0);
+    for (int64_t k = 0; k < K; ++k) std::memcpy(&ctx->sel_hV[(size_t)(k * Jp)], V + k * J, (size_t)J * 8);
+    if (!ctx->sel_V.ensure(nV * 8)) return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(V) failed");
+    FSNAP_HIP(hipMemcpyAsync(ctx->sel_V.p, ctx->sel_hV.data(), nV * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(V)");
+    FSNAP_HIP(fsnap::launch_sel_rows(ctx->dA, ctx->lda, m, (int)K, (const double*)ctx->sel_V.p, (int)Jp, (double*)ctx->sel_var.p,
+                                     ctx->stream),
+              "launch fsnap_sel_rows_k");
+    if ((rc = select_refresh(ctx))) return rc;
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");     // the staging of V may be reused
+    return FSNAP_OK;
+}
+
+int fsnap_select_state(fsnap_ctx* ctx, double* var, double* cat_sum, double* cat_max, int64_t* cat_count, int32_t* alive) {
+    if (!ctx) return FSNAP_E_ARG;
+    int rc = select_session(ctx, "fsnap_select_state");
+    if (rc) return rc;
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    const int ncat = ctx->sel_ncat;
+    const double* dcat = (const double*)ctx->sel_cat.p;
+    if (var && ctx->sel_m > 0)
+        FSNAP_HIP(hipMemcpyAsync(var, ctx->sel_var.p, (size_t)ctx->sel_m * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(var)");
+    if (cat_sum) FSNAP_HIP(hipMemcpyAsync(cat_sum, dcat, (size_t)ncat * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(sum)");
+    if (cat_max) FSNAP_HIP(hipMemcpyAsync(cat_max, dcat + ncat, (size_t)ncat * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(max)");
+    if (alive) FSNAP_HIP(hipMemcpyAsync(alive, ctx->sel_alive.p, (size_t)ncat * 4, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(alive)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    if (cat_count) std::memcpy(cat_count, ctx->sel_hcount.data(), (size_t)ncat * 8);
+    return FSNAP_OK;
+}
+
+int fsnap_select_end(fsnap_ctx* ctx) {
+    if (!ctx) return FSNAP_E_ARG;
+    ctx->sel_active = false;
+    return FSNAP_OK;
 }
 
 // ---- leave-one-configuration-out predictions of the resident training rows (kernels L1, L2 of fsnap_loco.hip) --------

@@ -124,6 +124,16 @@ struct fsnap_ctx {
     std::vector<int32_t> uq_hidx, uq_hcbeg;
     std::vector<int64_t> uq_hch, uq_hcount;
     bool uq_inflight = false;                     // copies out of the staging above may still be running
+    // fsnap_select_*: the session's resident per-row variances and scales, its own copy of the category layout, chunk
+    // partials, [cat_sum | cat_max], counts, live flags, the padded factor V and the (score, category) pair of a pick; the host
+    // keeps the counts and live flags too.  sel_active is cleared by everything that changes the rows (cand_forget).
+    DevBuf sel_var, sel_scale, sel_idx, sel_ch, sel_cbeg, sel_part, sel_cat, sel_count, sel_alive, sel_V, sel_out;
+    std::vector<double> sel_hV;
+    std::vector<int64_t> sel_hcount;
+    std::vector<int32_t> sel_halive;
+    bool sel_active = false, sel_has_scale = false;
+    int sel_ncat = 0, sel_objective = 0;
+    int64_t sel_m = 0, sel_nch = 0;
     // fsnap_loco_rows: [padded M | padded beta], sorted row index, configuration offsets and per-bin lists, zeta per position
     // (npos x Jp), (w, e, a . beta) per position, per-row predictions, per-configuration info, per-workgroup scratch (v; H of
     // the configurations too large for LDS); kept between calls like the other workspaces

@@ -205,6 +205,22 @@ hipError_t launch_uq_rows(int mode, const double* A, int64_t lda, int64_t m, int
 hipError_t launch_uq_cat(const double* var, const double* scale, const int* idx, const CatChunk* chunks, int64_t nchunks,
                          const int* cbeg, int ncat, double* part, double* cat_sum, double* cat_max, hipStream_t st);
 
+// Greedy batch selection (fsnap_select.hip).  Kernel B1 / B1G: var[i] -= ||a_i V||^2 in place (Vp: device, Kp x Jp row-major,
+// zero-padded as Mp of launch_uq_rows; the subtracted value has the bits of launch_uq_rows in NORM mode).
+hipError_t launch_sel_rows(const double* A, int64_t lda, int64_t m, int K, const double* Vp, int Jp, double* var,
+                           hipStream_t st);
+// kernels B2 + B3: launch_uq_cat over the categories with alive[c] != 0 (the others keep their cat_sum / cat_max)
+hipError_t launch_sel_scores(const double* var, const double* scale, const int* idx, const CatChunk* chunks, int64_t nchunks,
+                             const int* cbeg, const int* alive, int ncat, double* part, double* cat_sum, double* cat_max,
+                             hipStream_t st);
+// kernel B4: out[0] = best score over the live categories (SEL_SUM: cat_sum, SEL_MAX: cat_max, SEL_MEAN: cat_sum / count),
+// out[1] = its category as a double (ties: the lowest id; -1: none alive); retire != 0 clears alive[] of the winner
+constexpr int SEL_SUM = 0;
+constexpr int SEL_MAX = 1;
+constexpr int SEL_MEAN = 2;
+hipError_t launch_sel_pick(const double* cat_sum, const double* cat_max, const int64_t* count, int* alive, int ncat,
+                           int objective, int retire, double* out, hipStream_t st);
+
 // Leave-one-configuration-out predictions (fsnap_loco.hip).  Kernel L1: for the npos positions of the sorted row index idx,
 // Z[p] = a_idx[p] M (Jp doubles per position; Mp: device, Kp x Jp row-major, zero-padded as for launch_uq_rows), pb[p] =
 // a . beta (bp: Kp doubles), pw[p] = w_eff, pe[p] = w_eff b - w_eff (a . beta) from wpack (kernel 1A's pairs).

@@ -22,23 +22,18 @@
 // atomics; every result is written with vector stores.
 #include "fsnap_device_common.h"
 #include "fsnap_kernels.h"
+#include "fsnap_rowvar_body.h"
 
 namespace {
 
-constexpr int UQ_RB = 2;   // 16-row blocks per wave
+constexpr int UQ_RB = fsnap_rowvar::RB;   // 16-row blocks per wave
 
 template <int MODE>
 __device__ __forceinline__ double uq_fold(double v, double t, double a) {
-    if constexpr (MODE == fsnap::UQ_QUAD) return __builtin_fma(t, a, v);
-    else return __builtin_fma(t, t, v);
+    return fsnap_rowvar::fold<MODE>(v, t, a);
 }
 
-// sum over the four lanes e, e + 16, e + 32, e + 48 (fixed order)
-__device__ __forceinline__ double uq_ks_sum(double v) {
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
+__device__ __forceinline__ double uq_ks_sum(double v) { return fsnap_rowvar::ks_sum(v); }
 
 template <int NT, int MODE>
 __global__ __launch_bounds__(256, 2) void fsnap_uq_rows_k(const double* __restrict__ A, int64_t lda, int64_t m, int K,
@@ -114,100 +109,29 @@ __global__ __launch_bounds__(256, 2) void fsnap_uq_rows_k(const double* __restri
     }
 }
 
-// Kernel U1G: any K (untuned).  Same lane mapping; the row values are loaded per k step of every M tile.
+// Kernel U1G: any K (untuned).  Same lane mapping; the row values are loaded per k step of every M tile
+// (fsnap_rowvar::rows_gen_body, shared with kernel B1G of fsnap_select.hip).
 template <int MODE>
 __global__ __launch_bounds__(256) void fsnap_uq_rows_gen_k(const double* __restrict__ A, int64_t lda, int64_t m, int K,
                                                            const double* __restrict__ Mp, int Jp,
                                                            const double* __restrict__ bp, double* __restrict__ var,
                                                            double* __restrict__ preds) {
-    const int lane = threadIdx.x & 63, e = lane & 15, ks = lane >> 4, wave = threadIdx.x >> 6;
-    const int64_t row0 = ((int64_t)blockIdx.x * 4 + wave) * (16 * UQ_RB);
-    const int ns = (K + 3) / 4;
-    const double* src[UQ_RB];
-    int64_t row[UQ_RB];
-    bool valid[UQ_RB];
-#pragma unroll
-    for (int r = 0; r < UQ_RB; ++r) {
-        row[r] = row0 + 16 * r + e;
-        valid[r] = row[r] < m;
-        src[r] = A + (valid[r] ? row[r] : 0) * lda;
-    }
-    auto ld = [&](int r, int k) -> double { return (valid[r] && k < K) ? src[r][k] : 0.0; };
-    if (preds) {
-#pragma unroll
-        for (int r = 0; r < UQ_RB; ++r) {
-            double p = 0.0;
-            for (int s = 0; s < ns; ++s) p = __builtin_fma(ld(r, 4 * s + ks), bp[4 * s + ks], p);
-            p = uq_ks_sum(p);
-            if (ks == 0 && valid[r]) preds[row[r]] = p;
-        }
-    }
-    if (!var) return;
-    double v[UQ_RB];
-#pragma unroll
-    for (int r = 0; r < UQ_RB; ++r) v[r] = 0.0;
-    const int njt = Jp / 16;
-    for (int jt = 0; jt < njt; ++jt) {
-        d4 acc[UQ_RB];
-#pragma unroll
-        for (int r = 0; r < UQ_RB; ++r) acc[r] = d4{0.0, 0.0, 0.0, 0.0};
-        const double* mcol = Mp + 16 * jt + e;
-        for (int s = 0; s < ns; ++s) {
-            const double mf = mcol[(int64_t)(4 * s + ks) * Jp];
-#pragma unroll
-            for (int r = 0; r < UQ_RB; ++r) acc[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(mf, ld(r, 4 * s + ks), acc[r], 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < UQ_RB; ++r)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                v[r] = uq_fold<MODE>(v[r], acc[r][g], MODE == fsnap::UQ_QUAD ? ld(r, 16 * jt + ks + 4 * g) : 0.0);
-    }
-#pragma unroll
-    for (int r = 0; r < UQ_RB; ++r) {
-        const double s = uq_ks_sum(v[r]);
-        if (ks == 0 && valid[r]) var[row[r]] = s;
-    }
+    fsnap_rowvar::rows_gen_body<MODE, false>(A, lda, m, K, Mp, Jp, bp, var, preds);
 }
 
 // Kernel U2: one wave per chunk; lane l takes positions l, l + 64, ... of the chunk in order, then a fixed butterfly.
-// part[chunk][2] = (sum, max) of s_i v_i over the chunk's rows (s = 1 without a scale).
+// part[chunk][2] = (sum, max) of s_i v_i over the chunk's rows (s = 1 without a scale).  (fsnap_rowvar::chunk_body, shared
+// with kernel B2 of fsnap_select.hip.)
 __global__ __launch_bounds__(64) void fsnap_uq_chunk_k(const double* __restrict__ var, const double* __restrict__ scale,
                                                        const int* __restrict__ idx, const fsnap::CatChunk* __restrict__ chunks,
                                                        double* __restrict__ part) {
-    const fsnap::CatChunk ch = chunks[blockIdx.x];
-    const int lane = threadIdx.x;
-    double s = 0.0, mx = -__builtin_inf();
-    for (int p = lane; p < ch.count; p += 64) {
-        const int r = idx[ch.first + p];
-        const double val = scale ? scale[r] * var[r] : var[r];
-        s += val;
-        mx = val > mx ? val : mx;
-    }
-    for (int o = 1; o < 64; o <<= 1) {
-        s += __shfl_xor(s, o, 64);
-        const double om = __shfl_xor(mx, o, 64);
-        mx = om > mx ? om : mx;
-    }
-    if (lane == 0) {
-        part[2 * (int64_t)blockIdx.x] = s;
-        part[2 * (int64_t)blockIdx.x + 1] = mx;
-    }
+    fsnap_rowvar::chunk_body(var, scale, idx, chunks, nullptr, part);
 }
 
 // Kernel U3: one thread per category, its chunks in order (cbeg[ncat + 1]); an empty category gets (0, -inf).
 __global__ __launch_bounds__(256) void fsnap_uq_cat_k(const double* __restrict__ part, const int* __restrict__ cbeg, int ncat,
                                                      double* __restrict__ cat_sum, double* __restrict__ cat_max) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= ncat) return;
-    double s = 0.0, mx = -__builtin_inf();
-    for (int ch = cbeg[c]; ch < cbeg[c + 1]; ++ch) {
-        s += part[2 * (int64_t)ch];
-        const double om = part[2 * (int64_t)ch + 1];
-        mx = om > mx ? om : mx;
-    }
-    if (cat_sum) cat_sum[c] = s;
-    if (cat_max) cat_max[c] = mx;
+    fsnap_rowvar::cat_body(part, cbeg, nullptr, ncat, cat_sum, cat_max);
 }
 
 }  // namespace

@@ -30,6 +30,7 @@ class ANL(Solver):
         bp = sse / 2.0
         ap = (npt - nbas) / 2.0
         sigmahat = bp / (ap - 1.0)
+        self.sigmahat = float(sigmahat)             # the noise variance Solver.select_batch conditions on
         if pt._rank != 0:
             return
         self.fit = fit

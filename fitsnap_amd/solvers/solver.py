@@ -25,7 +25,7 @@ import numpy as np
 
 from .. import _capi
 from .._hostblas import blas_threads
-from . import loco, uq
+from . import loco, select, uq
 
 
 class _TrainWeights:
@@ -159,6 +159,7 @@ class Solver:
         self.linear = linear
         self.cov = None
         self.fit_sam = None
+        self.sigmahat = None         # noise variance of the last ANL fit (cov = sigmahat * pinv(G + nugget I)); select_batch
         # engine state
         self.keep_resident = False   # explicit-array mode: reuse the HBM copy of (a, b) across calls
         self.refine_steps = 0        # iterative-refinement steps after the K x K solve (SVD sets 2)
@@ -1078,6 +1079,26 @@ class Solver:
             with np.errstate(invalid="ignore", divide="ignore"):
                 res["cat_mean"] = res["cat_sum"] / res["cat_count"]
         return res
+
+    # ------------------------------------------------------------------------------
+    # greedy active-learning batch selection (solvers/select.py, csrc/fsnap_select.hip)
+    # ------------------------------------------------------------------------------
+    def select_batch(self, batch_size, a=None, w=None, categories=None, row_scale=None, objective="sum", noise=None,
+                     cov=None):
+        """Pick ``batch_size`` units of a pool one after the other, each against the posterior that already contains the
+        units picked before it (greedy variance reduction; exact for a linear model, no refit, no labels needed) -- the
+        batch step of the Bayesian active-learning loop (bayesian_active_learning.py:887-909) without the k-means
+        de-duplication the reference needs on top of one ranking.
+
+        ``a``, ``categories`` (required: the units) and ``row_scale`` as in ``prediction_variance``; ``w``: the weights the
+        pool rows would carry in a fit (``a=None``: the shared ``w``; otherwise ones).  ``objective``: "sum", "max" or
+        "mean" ("average") of s_i var_i over a unit's rows.  ``noise``: the noise variance of a unit-weight row (default:
+        the sigma^2 of the last ANL fit); ``cov``: the posterior covariance (default ``self.cov``).  Collective on several
+        ranks (every unit must live on one rank; ``cov`` and ``noise`` are rank 0's); ties go to the first key in
+        rank-major key order.  Returns ``select.BatchSelection(keys, scores, all_keys, initial_scores, var, cov, ranks)``;
+        fewer than ``batch_size`` picks when the pool has fewer units.  Raises ValueError without a covariance or a noise
+        variance."""
+        return select.select_batch(self, batch_size, a, w, categories, row_scale, objective, noise, cov)
 
     # ------------------------------------------------------------------------------
     # leave-one-configuration-out errors (solvers/loco.py, csrc/fsnap_loco.hip)

@@ -310,6 +310,44 @@ int fsnap_row_variance_device(fsnap_ctx* ctx, int mode, int64_t K, int64_t J, co
                               const double* d_scale, const int32_t* cat, int ncat, double* d_var, double* d_preds,
                               double* d_cat_sum, double* d_cat_max, int64_t* d_cat_count);
 
+/* Greedy batch selection for active learning on the resident rows (kernels B1 ... B4 of csrc/fsnap_select.hip; the host
+ * algebra is solvers/select.py).  A session keeps var_i = a_i^T C_t a_i of every row, and per category c the sum / max /
+ * count of scale_i var_i, on the context; picking a unit changes the posterior to C_t - V V^T, which costs one pass over
+ * the rows, and nothing but one (category, score) pair per pick comes back to the host.
+ *   fsnap_select_begin     mode, K, J, M, scale, cat, ncat as in fsnap_row_variance (cat is required, ncat >= 1): the initial
+ *                          variances and category sums ARE those of fsnap_row_variance (same kernels, same bits), left on the
+ *                          device.  objective: the score of a category, FSNAP_SELECT_SUM (cat_sum), _MAX (cat_max) or _MEAN
+ *                          (cat_sum / cat_count).  Every category with at least one row starts alive.  A running session is
+ *                          replaced.
+ *   fsnap_select_pick      *category = the live category of the largest score (ties: the lowest id; a NaN score ranks
+ *                          lowest), *score = its score; -1 (score 0) when no category is alive.  The arg-max runs on the
+ *                          device.  retire != 0 takes the winner out of the session (it is never returned again);
+ *                          retire = 0 only looks (several ranks: the ranks compare their winners first).
+ *   fsnap_select_retire    takes a live category out of the session (FSNAP_E_ARG when it is not alive).
+ *   fsnap_select_downdate  V (host, K x J row-major, any J >= 1; copied padded to 16-multiples): var_i <- var_i - ||a_i V||^2
+ *                          for every row (kernel B1, fp64 MFMA, K <= 144; B1G, untuned, beyond), then the sums / maxima of
+ *                          the live categories again (retired categories keep the values they were retired with).  The
+ *                          subtracted value has the bits of fsnap_row_variance(FSNAP_UQ_NORM, V); a row's new variance
+ *                          depends on a_i, its old variance and V alone: bit-identical run to run and under any row
+ *                          subset, order, m or lda; category sums in stable-sorted row order.  No atomics.
+ *   fsnap_select_state     downloads var (m doubles), cat_sum, cat_max (ncat doubles), cat_count (ncat int64) and alive
+ *                          (ncat int32, 1 / 0); every output may be NULL.
+ *   fsnap_select_end       drops the session.
+ * Anything that replaces the resident rows or prepares a category layout (fsnap_upload_rows, fsnap_bind_rows,
+ * fsnap_rows_alloc, fsnap_drop_rows, fsnap_assemble, fsnap_cat_prepare) ends the session: pick, retire, downdate and state
+ * then return FSNAP_E_ARG, as they do without a session.  fsnap_row_variance and the fits leave it alone.  With no rows
+ * (m = 0) a session has no live category.  Host in and out, synchronous. */
+#define FSNAP_SELECT_SUM 0
+#define FSNAP_SELECT_MAX 1
+#define FSNAP_SELECT_MEAN 2
+int fsnap_select_begin(fsnap_ctx* ctx, int mode, int64_t K, int64_t J, const double* M, const double* scale, const int32_t* cat,
+                       int ncat, int objective);
+int fsnap_select_pick(fsnap_ctx* ctx, int retire, int32_t* category, double* score);
+int fsnap_select_retire(fsnap_ctx* ctx, int32_t category);
+int fsnap_select_downdate(fsnap_ctx* ctx, int64_t K, int64_t J, const double* V);
+int fsnap_select_state(fsnap_ctx* ctx, double* var, double* cat_sum, double* cat_max, int64_t* cat_count, int32_t* alive);
+int fsnap_select_end(fsnap_ctx* ctx);
+
 /* Exact leave-one-configuration-out (LOCO) predictions of a linear smoother from the resident training rows (kernels L1, L2 of
  * csrc/fsnap_loco.hip, fp64 MFMA; no refit).  M (host, K x J row-major) is any factor of C = (G + alpha I)^-1 = M M^T of the
  * fit (RIDGE: its alpha; ANL: pinv with cov_nugget; SVD: alpha = 0, or V_r Lambda_r^-1/2 of the kept directions), beta
