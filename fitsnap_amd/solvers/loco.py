@@ -1,7 +1,8 @@
 """Exact leave-one-configuration-out (LOCO) errors of the linear smoothers (SVD, RIDGE, ANL) without refits.
 
 For the weighted training rows x_i = w_i a_i, y_i = w_i b_i of a fit, G = sum x_i x_i^T and C = (G + alpha I)^-1 = M M^T
-(RIDGE: its alpha; ANL: pinv(G + cov_nugget I); SVD: alpha = 0, or the kept directions of a truncated / row-space fit),
+(RIDGE: its alpha; ANL: pinv(G + cov_nugget I); SVD: alpha = 0, or the kept directions of a truncated fit; a row-space fit
+takes M from the triangle of the rows, ``rows_triangle`` / ``factor_triangle``, since its G is too ill-conditioned),
 every row i of a unit c (a configuration, or any label such as a group) has the prediction of the fit without c's rows
 
     zeta_i = a_i M,  z_i = w_i zeta_i,  e_i = y_i - x_i . beta,  S_c = Z_c^T Z_c
@@ -73,6 +74,41 @@ def factor_eigen(G, alpha=0.0, rank=None, scaled=True, rcond=PINV_RCOND):
     return M
 
 
+def rows_triangle(A, w_eff, parts=None):
+    """R of A_w = Q R for the weighted rows A_w = w_eff a (Householder QR on the host); with ``parts`` (the triangles of
+    other row blocks, e.g. one per rank) the triangle of all blocks stacked.  R^T R = G without ever forming G."""
+    blocks = [] if parts is None else [np.asarray(p, dtype=np.float64) for p in parts]
+    if A is not None:
+        A = np.asarray(A, dtype=np.float64)
+        blocks.append(A * np.asarray(w_eff, dtype=np.float64).reshape(-1, 1))
+    stack = np.vstack(blocks)
+    if stack.shape[0] == 0:
+        return stack
+    with blas_threads(stack.shape[1]):
+        return np.linalg.qr(stack, mode="r")
+
+
+def factor_triangle(R, rank=None):
+    """M = V_r Sigma_r^-1 of the largest ``rank`` singular triplets of R (A_w = Q R, ``rows_triangle``): M M^T is the
+    pseudo-inverse of G on the kept directions and M^T G M = I to kappa(A_w) eps.  The eigenpairs of G itself
+    (``factor_eigen``) are good to kappa(A_w)^2 eps only: from kappa ~ 1e8 on, where an SVD fit takes the row-space path,
+    the weakest kept column of M would be wrong in its leading digits."""
+    R = np.asarray(R, dtype=np.float64)
+    K = R.shape[1]
+    if R.shape[0] == 0:
+        return np.zeros((K, 1))
+    with blas_threads(K):
+        _, sv, Vt = np.linalg.svd(R, full_matrices=False)
+    used = sv > 0.0
+    if rank is not None:
+        used &= np.arange(sv.size) < int(rank)
+    r = int(np.count_nonzero(used))
+    M = np.zeros((K, max(r, 1)))
+    if r:
+        M[:, :r] = Vt[used].T / sv[used][None, :]
+    return M
+
+
 def check_smoother(solver):
     """Kind of a solver whose fit is a linear smoother of the rows; ValueError for any other solver (ARD, LASSO, MERR,
     MCMC) and for fits through ``apply_transpose``."""
@@ -85,8 +121,10 @@ def check_smoother(solver):
     return kind
 
 
-def smoother_factor(solver):
-    """(kind, M) of a fitted SVD / RIDGE / ANL solver (on the rank that holds the statistics)."""
+def smoother_factor(solver, triangle=None):
+    """(kind, M) of a fitted SVD / RIDGE / ANL solver (on the rank that holds the statistics).  ``triangle``: R of the
+    weighted training rows (``rows_triangle``), used for an SVD fit that took the row-space path -- its statistics are too
+    ill-conditioned for a factor from G (``factor_triangle``); ``loco_errors`` passes it."""
     kind = check_smoother(solver)
     sec = solver.config.sections
     stats = solver.last_statistics
@@ -111,6 +149,8 @@ def smoother_factor(solver):
         except np.linalg.LinAlgError:
             pass
     kept = None if rank is None or rank < 0 else min(int(rank), K - zero_cols)
+    if solver.last_row_space is not None and triangle is not None:
+        return kind, factor_triangle(triangle, rank=kept)
     return kind, factor_eigen(G, 0.0, rank=kept, rcond=0.0)
 
 
@@ -206,11 +246,8 @@ def loco_errors(solver, by="Configs", fs_dict=None, b=None, w=None):
     from pandas import DataFrame
 
     pt = solver.pt
-    check_smoother(solver)                                  # every rank refuses alike
-    M = smoother_factor(solver)[1] if pt._rank == 0 else None
+    kind = check_smoother(solver)                           # every rank refuses alike
     fit = solver._uq_inputs()[1]                            # broadcast from rank 0, B0 zeros of _offset taken out
-    if pt.multi:
-        M = pt.bcast_object(M, src=0)
     if fit is None:
         raise RuntimeError("loco_errors: call perform_fit first")
     beta = np.asarray(fit, dtype=np.float64).reshape(-1)
@@ -241,11 +278,21 @@ def loco_errors(solver, by="Configs", fs_dict=None, b=None, w=None):
     sorted_rows, offsets, units = unit_index(labels[by], train)
     if pt.multi:
         check_units_disjoint(pt.allgather_object(units))
+    ctx = pt.hip() if m > 0 else None
+    if m > 0 and (ctx.m != m or ctx.K != beta.shape[0]):
+        raise RuntimeError(f"loco_errors: the resident rows ({ctx.m} x {ctx.K}) are not those of the fit ({m} rows, "
+                           f"{beta.shape[0]} columns): call perform_fit first")
+    triangle = None
+    if kind == "SVD" and solver.last_row_space is not None:
+        # a fit on the rows (every rank took that path): M from the rows too, through their triangle
+        triangle = rows_triangle(ctx.download_rows(want_b=False, want_w=False)[0] if m > 0 else np.zeros((0, beta.shape[0])),
+                                 np.where(train, w, 0.0))
+        if pt.multi:
+            triangle = rows_triangle(None, None, pt.allgather_object(triangle))
+    M = smoother_factor(solver, triangle)[1] if pt._rank == 0 else None
+    if pt.multi:
+        M = pt.bcast_object(M, src=0)
     if m > 0:
-        ctx = pt.hip()
-        if ctx.m != m or ctx.K != M.shape[0]:
-            raise RuntimeError(f"loco_errors: the resident rows ({ctx.m} x {ctx.K}) are not those of the fit ({m} rows, "
-                               f"{M.shape[0]} columns): call perform_fit first")
         preds, info = ctx.loco_rows(M, beta, sorted_rows, offsets)
     else:
         preds, info = np.zeros(0), np.zeros((0, 4))

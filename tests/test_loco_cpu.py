@@ -1,12 +1,19 @@
 """CPU: the host side of the leave-one-configuration-out errors (fitsnap_amd/solvers/loco.py) -- both closed forms (J space
 and n space) against brute-force refits without each unit, the factors M of C = (G + alpha I)^-1, the unit index, the
-table assembly, and the refusal paths."""
+table assembly, and the refusal paths; the long-double reference and the bars of the kernel tests (tests/loco_cases.py)
+on loco_host, and on three subtly wrong variants of it that the bars must catch."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 from fitsnap_amd.config import Config
 from fitsnap_amd.parallel_tools import ParallelTools
 from fitsnap_amd.solvers import loco, solver_factory
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import loco_cases as lc  # noqa: E402
 
 
 def problem(seed, K, sizes, zero_w=0, testing=0):
@@ -173,3 +180,123 @@ def test_a_unit_split_across_ranks_is_refused():
     loco.check_units_disjoint([["c0", "c2"], ["c1", "c3"]])
     with pytest.raises(ValueError, match="'c2' has rows on ranks 0 and 1"):
         loco.check_units_disjoint([["c0", "c2"], ["c1", "c2"]])
+
+
+# ---- the reference and the bars of tests/test_gpu_loco.py ----------------------------------------------------------------
+
+def test_long_double_cholesky_solve_and_refit():
+    lc.need_long_double()
+    rng = np.random.default_rng(1)
+    X = rng.standard_normal((40, 12))
+    H = X.T @ X
+    L, piv, ok = lc.cholesky_ld(H)
+    assert ok and L.dtype == np.longdouble and np.all(np.triu(L, 1) == 0)
+    assert float(np.max(np.abs(L @ L.T - H))) <= 1e-17 * np.max(np.abs(H))
+    np.testing.assert_allclose(piv.astype(float), loco._cholesky_pivots(H), rtol=1e-12)
+    r = rng.standard_normal(12)
+    x = lc.solve_ld(H, r)
+    assert float(np.max(np.abs(H.astype(np.longdouble) @ x - r))) <= 1e-17 * np.max(np.abs(r)) * np.linalg.cond(H)
+    _, piv, ok = lc.cholesky_ld(np.diag([1.0, 0.0, 2.0]))
+    assert not ok and piv.tolist() == [1.0, 0.0, 0.0]
+    with pytest.raises(np.linalg.LinAlgError):
+        lc.solve_ld(np.diag([1.0, -1.0]), np.ones(2))
+    # the refit: J = K against the float64 downdated solve, J < K against lstsq in the projected features
+    A, b, w, _ = lc.config_rows(4, 9, [30, 7, 12, 25])
+    rows = np.arange(30, 37)
+    np.testing.assert_allclose(lc.brute_force_ld(A, b, w, rows, 1e-4), lc.downdated(A, b, w, rows, 1e-4), rtol=0, atol=1e-12)
+    Aw = A * w[:, None]
+    M = loco.factor_eigen(Aw.T @ Aw, 0.0, rank=5)
+    keep = np.setdiff1d(np.arange(len(b)), rows)
+    gamma = np.linalg.lstsq(Aw[keep] @ M, (b * w)[keep], rcond=None)[0]
+    np.testing.assert_allclose(lc.brute_force_ld(A, b, w, rows, 0.0, M), A[rows] @ M @ gamma, rtol=0, atol=1e-12)
+    np.testing.assert_allclose(lc.Refit(A, b, w, 0.0, M, project_rows=True).predict(rows), A[rows] @ M @ gamma, rtol=0,
+                               atol=1e-12)
+
+
+def wrong_closed_form(A, b, w, M, beta, rows, off, defect):
+    """loco_host's closed form with one defect: "zeta32" (zeta rounded through float32), "column" (the last column of M
+    dropped) or "row" (the last row of each unit left out of the Gram matrix and the right-hand side, but predicted);
+    None: no defect."""
+    if defect == "column":
+        M = M[:, :-1]
+    J = M.shape[1]
+    pred = np.full(len(b), np.nan)
+    for c in range(len(off) - 1):
+        r = rows[off[c]:off[c + 1]]
+        zeta = A[r] @ M
+        if defect == "zeta32":
+            zeta = zeta.astype(np.float32).astype(np.float64)
+        pb = A[r] @ beta
+        Z = w[r, None] * zeta
+        e = w[r] * b[r] - w[r] * pb
+        if defect == "row":
+            Z, e = Z[:-1], e[:-1]
+        n = Z.shape[0]
+        if n <= J:
+            v = Z.T @ np.linalg.solve(np.eye(n) - Z @ Z.T, e)
+        else:
+            v = np.linalg.solve(np.eye(J) - Z.T @ Z, Z.T @ e)
+        pred[r] = pb - zeta @ v
+    return pred
+
+
+@pytest.mark.parametrize("K", [31, 142, 150])
+@pytest.mark.parametrize("alpha", lc.SWEEP_ALPHA)
+def test_the_bars_of_the_kernel_tests_pass_loco_host_and_catch_three_defects(K, alpha):
+    """The reduced sweep (the sizes and the J of tests/test_gpu_loco.py's sweep): loco_host passes the a-priori bar, the RMS
+    condition and the pivot bound in every cell; a closed form with zeta through float32, without the last column of M, or
+    without each unit's last row in the Gram matrix breaks the a-priori bar in every cell."""
+    A, b, w, G, c, stats = lc.sweep_rows(K)
+    m = len(b)
+    rows = np.arange(m, dtype=np.int32)
+    for J in lc.sweep_js(K):
+        off, _ = lc.sweep_units(K, J, m)
+        M, beta = lc.sweep_factor(G, c, alpha, J, stats)
+        host, hinfo = loco.loco_host(A, b, w, M, beta, rows, off)
+        res = lc.measure_cell(A, b, w, alpha, M, beta, rows, off, host, stats, host=host)
+        print(lc.cell_line(f"host K={K} alpha={alpha:g} J={J}", res))
+        assert np.min(res["lam_min"]) >= lc.LAM_MIN
+        assert np.max(res["ratio"]) <= 1.0 and res["rms_pred"] <= lc.RMS_FACTOR * res["rms_host"]
+        assert np.all(np.abs(hinfo[:, 1] - res["piv"]) <= 4 * (J + res["d"]) * lc.EPS)
+        assert np.max(res["abs"]) <= 1e-9 * np.max(np.abs(b))
+        same = wrong_closed_form(A, b, w, M, beta, rows, off, None)
+        assert np.max(np.abs(same - host) / res["bar"]) <= 0.1          # the stand-in is the closed form
+        for defect in ("zeta32", "column", "row"):
+            wrong = wrong_closed_form(A, b, w, M, beta, rows, off, defect)
+            excess = np.abs(wrong - res["truth"]) / res["bar"]
+            assert np.max(excess) > 1.0, (defect, J, np.max(excess))
+            # not one lucky row: the defect shows in most units
+            bad = [np.max(excess[off[u]:off[u + 1]]) > 1.0 for u in range(len(off) - 1)]
+            assert np.mean(bad) >= 0.5, (defect, J, np.mean(bad))
+
+
+def test_factor_from_the_rows_triangle_where_the_statistics_are_too_ill_conditioned():
+    # kappa(A_w) = 1e8: M^T G M = I holds for the factor from the rows, not for the eigenpairs of G (kappa^2 eps ~ 1)
+    rng = np.random.default_rng(2)
+    m, K = 1500, 12
+    U, _ = np.linalg.qr(rng.standard_normal((m, K)))
+    V, _ = np.linalg.qr(rng.standard_normal((K, K)))
+    sv = np.ones(K)
+    sv[-1] = 1e-8
+    A = (U * sv) @ V.T
+    w = rng.uniform(0.5, 2.0, m)
+    b = A @ rng.standard_normal(K) + 1e-3 * rng.standard_normal(m)
+    R = loco.rows_triangle(A, w)
+    parts = [loco.rows_triangle(A[:400], w[:400]), loco.rows_triangle(A[400:], w[400:]), np.zeros((0, K))]
+    Xl = (A * w[:, None]).astype(np.longdouble)
+    for tri in (R, loco.rows_triangle(None, None, parts)):
+        M = loco.factor_triangle(tri)
+        T = Xl @ M.astype(np.longdouble)
+        assert M.shape == (K, K) and float(np.max(np.abs(T.T @ T - np.eye(K)))) <= 1e-6
+    assert loco.factor_triangle(R, rank=K - 1).shape == (K, K - 1)
+    assert np.all(loco.factor_triangle(np.zeros((0, K))) == 0.0)
+    # LOO predictions with it against the long-double refit in the projected features
+    sizes = [1, 5, 12, 13, 40, 100] * 8 + [132]
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    rows = np.arange(m, dtype=np.int32)
+    beta = np.linalg.lstsq(A * w[:, None], b * w, rcond=1e-13)[0]
+    pred, info = loco.loco_host(A, b, w, M, beta, rows, off)
+    refit = lc.Refit(A, b, w, 0.0, M, projected=True, project_rows=True)
+    truth = np.concatenate([refit.predict(rows[off[u]:off[u + 1]]) for u in range(len(sizes))])
+    assert np.all(info[:, 2] == 1.0)
+    assert np.max(np.abs(pred - truth)) <= 1e-6 * np.max(np.abs(truth))
