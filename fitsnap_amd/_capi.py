@@ -129,6 +129,11 @@ SIGNATURES = {
     "fsnap_select_downdate": (c_int, [c_void_p, c_int64, c_int64, c_void_p]),
     "fsnap_select_state": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fsnap_select_end": (c_int, [c_void_p]),
+    "fsnap_joint_begin": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "fsnap_joint_score": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_double, c_void_p, c_void_p,
+                                  c_void_p]),
+    "fsnap_joint_retire": (c_int, [c_void_p, c_int64]),
+    "fsnap_joint_end": (c_int, [c_void_p]),
 }
 
 _lib = None
@@ -892,6 +897,57 @@ class HipContext:
     def select_end(self):
         """Drop the selection session (``fsnap_select_end``)."""
         self._check(self._lib.fsnap_select_end(self._h))
+
+    # -- joint unit scores (fsnap_joint_*) --------------------------------------------------
+    def joint_begin(self, sorted_rows, unit_offsets, omega=None):
+        """Start a joint-score session on the resident rows (``fsnap_joint_begin``): the rows of unit u are
+        ``sorted_rows[unit_offsets[u]:unit_offsets[u + 1]]``, ``omega`` (one per resident row, None = 1) their weights."""
+        rows = np.ascontiguousarray(sorted_rows, dtype=np.int32).reshape(-1)
+        off = np.ascontiguousarray(unit_offsets, dtype=np.int64).reshape(-1)
+        if off.size < 1:
+            raise ValueError("unit_offsets needs nunits + 1 entries")
+        if off[-1] != rows.size:
+            raise ValueError(f"unit_offsets ends at {off[-1]}, sorted_rows has {rows.size} entries")
+        if omega is not None:
+            omega = _f64(omega, "omega").reshape(-1)
+            if omega.shape != (self.m,):
+                raise ValueError(f"omega has shape {omega.shape}, expected ({self.m},)")
+        self._check(self._lib.fsnap_joint_begin(self._h, _ptr(rows) if rows.size else None, _ptr(off), off.size - 1, _ptr(omega)))
+        self._joint_units = off.size - 1
+
+    def joint_score(self, M, tau, B=None, want_gain=True, want_reduction=None):
+        """Scores of the session's live units under C = M M^T (M: K x J) and noise variance ``tau`` (``fsnap_joint_score``):
+        dict of "gain", "reduction" (None where not asked for; the reduction needs the target block B = M^T R^T, J x r) and
+        "info" (nunits x 4: dim S, n space, smallest pivot, rows).  Units that are not alive get NaN."""
+        M = _f64(M, "M")
+        if M.ndim == 1:
+            M = M.reshape(-1, 1)
+        if M.ndim != 2:
+            raise ValueError("M must be 2-D")
+        K, J = M.shape
+        r = 0
+        if B is not None:
+            B = _f64(B, "B")
+            if B.ndim != 2 or B.shape[0] != J:
+                raise ValueError(f"B must have shape ({J}, r)")
+            r = B.shape[1]
+        if want_reduction is None:
+            want_reduction = B is not None
+        nu = getattr(self, "_joint_units", 0)
+        gain = np.empty(nu) if want_gain else None
+        red = np.empty(nu) if want_reduction else None
+        info = np.full((nu, 4), np.nan)
+        self._check(self._lib.fsnap_joint_score(self._h, K, J, _ptr(M), r, _ptr(B) if r else None, float(tau), _ptr(gain),
+                                                _ptr(red), _ptr(info)))
+        return {"gain": gain, "reduction": red, "info": info}
+
+    def joint_retire(self, unit):
+        """Take a live unit out of the session (``fsnap_joint_retire``)."""
+        self._check(self._lib.fsnap_joint_retire(self._h, int(unit)))
+
+    def joint_end(self):
+        """Drop the joint-score session (``fsnap_joint_end``)."""
+        self._check(self._lib.fsnap_joint_end(self._h))
 
     def loco_rows(self, M, beta, sorted_rows, cfg_offsets):
         """Leave-one-configuration-out predictions of the resident training rows (``fsnap_loco_rows``): M (K x J) with

@@ -388,6 +388,7 @@ int staged_rows_h2d(fsnap_ctx* ctx, void* dst, const void* src, size_t rows, siz
 // the category layout of the candidate kernels belongs to the rows it was prepared for: any change of the resident rows drops it
 void cand_forget(fsnap_ctx* ctx) {
     ctx->sel_active = false;          // a selection session (fsnap_select_*) belongs to the rows as well
+    ctx->joint_active = false;        // ... and so does a joint-score session (fsnap_joint_*)
     ctx->cand_layout = 0;
     ctx->cand_dA = nullptr;
     ctx->cand_stats_K = 0;
@@ -2755,5 +2756,181 @@ int fsnap_loco_rows(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, const
     FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
     for (int64_t c = 0; c < ncfg; ++c)
         if (cfg_offsets[c + 1] > cfg_offsets[c]) std::memcpy(cfg_info_out + 4 * c, &ctx->loco_hinfo[(size_t)(4 * c)], 32);
+    return FSNAP_OK;
+}
+
+// ---- joint information-gain / variance-reduction scores of units (kernels J1, J2 of fsnap_joint.hip) ------------------
+
+namespace {
+
+int joint_session(fsnap_ctx* ctx, const char* who) {
+    if (!ctx->joint_active)
+        return ctx->fail(FSNAP_E_ARG, "%s: no joint-score session (fsnap_joint_begin; new rows or a new category layout end one)", who);
+    return FSNAP_OK;
+}
+
+}  // namespace
+
+int fsnap_joint_begin(fsnap_ctx* ctx, const int32_t* sorted_rows, const int64_t* unit_offsets, int64_t nunits, const double* omega) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_joint_begin";
+    ctx->joint_active = false;
+    if (!unit_offsets) return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
+    if (nunits < 0 || nunits > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: nunits = %lld", who, (long long)nunits);
+    const int64_t m = ctx->m;
+    if (m > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: needs m < 2^31", who);
+    if (unit_offsets[0] != 0) return ctx->fail(FSNAP_E_ARG, "%s: unit_offsets[0] = %lld", who, (long long)unit_offsets[0]);
+    for (int64_t u = 0; u < nunits; ++u)
+        if (unit_offsets[u + 1] < unit_offsets[u]) return ctx->fail(FSNAP_E_ARG, "%s: unit_offsets decrease at %lld", who, (long long)u);
+    const int64_t npos = unit_offsets[nunits];
+    if (npos > m) return ctx->fail(FSNAP_E_ARG, "%s: %lld positions for %lld rows", who, (long long)npos, (long long)m);
+    if (npos > 0 && !sorted_rows) return ctx->fail(FSNAP_E_ARG, "%s: sorted_rows is NULL", who);
+    std::vector<double> hom((size_t)std::max<int64_t>(npos, 1), 1.0);
+    {   // every position names a distinct row of the context
+        std::vector<unsigned char> seen((size_t)std::max<int64_t>(m, 1), 0);
+        for (int64_t p = 0; p < npos; ++p) {
+            const int32_t r = sorted_rows[p];
+            if (r < 0 || r >= m || seen[(size_t)r])
+                return ctx->fail(FSNAP_E_ARG, "%s: sorted_rows[%lld] = %d is out of range or repeated", who, (long long)p, r);
+            seen[(size_t)r] = 1;
+            if (omega) hom[(size_t)p] = omega[r];
+        }
+    }
+    if (npos > 0) {
+        int rc = check_rows(ctx);
+        if (rc) return rc;
+    }
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    if (!ctx->joint_idx.ensure((size_t)std::max<int64_t>(npos, 1) * 4) || !ctx->joint_off.ensure((size_t)(nunits + 1) * 8) ||
+        !ctx->joint_om.ensure((size_t)std::max<int64_t>(npos, 1) * 8))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(joint) failed");
+    if (npos > 0) {
+        FSNAP_HIP(hipMemcpyAsync(ctx->joint_idx.p, sorted_rows, (size_t)npos * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(idx)");
+        FSNAP_HIP(hipMemcpyAsync(ctx->joint_om.p, hom.data(), (size_t)npos * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(omega)");
+    }
+    FSNAP_HIP(hipMemcpyAsync(ctx->joint_off.p, unit_offsets, (size_t)(nunits + 1) * 8, hipMemcpyHostToDevice, ctx->stream),
+              "hipMemcpy(offsets)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    ctx->joint_hoff.assign(unit_offsets, unit_offsets + nunits + 1);
+    ctx->joint_halive.assign((size_t)nunits, 0);
+    for (int64_t u = 0; u < nunits; ++u) ctx->joint_halive[(size_t)u] = unit_offsets[u + 1] > unit_offsets[u];   // an empty unit is never scored
+    ctx->joint_m = m;
+    ctx->joint_npos = npos;
+    ctx->joint_nunits = nunits;
+    ctx->joint_active = true;
+    return FSNAP_OK;
+}
+
+int fsnap_joint_score(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, int64_t r, const double* B, double tau,
+                      double* gain, double* reduction, double* info) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_joint_score";
+    int rc = joint_session(ctx, who);
+    if (rc) return rc;
+    if (!M) return ctx->fail(FSNAP_E_ARG, "%s: M is NULL", who);
+    if (K < 1 || K > 0x3FFFFFFF || J < 1 || J > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: K = %lld, J = %lld", who, (long long)K, (long long)J);
+    if (r < 0 || r > 0x3FFFFFFF || (r > 0 && !B)) return ctx->fail(FSNAP_E_ARG, "%s: r = %lld without B", who, (long long)r);
+    if (!B) r = 0;
+    if (reduction && r == 0) return ctx->fail(FSNAP_E_ARG, "%s: the reduction needs a target (B, r >= 1)", who);
+    if (!reduction) r = 0;
+    if (!(tau > 0.0) || tau == std::numeric_limits<double>::infinity()) return ctx->fail(FSNAP_E_ARG, "%s: tau = %g", who, tau);
+    const int64_t nunits = ctx->joint_nunits, npos = ctx->joint_npos;
+    if (npos > 0 && (ctx->joint_m != ctx->m || K != ctx->K))
+        return ctx->fail(FSNAP_E_ARG, "%s: K = %lld, the resident rows have %lld columns", who, (long long)K, (long long)ctx->K);
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int64_t u = 0; u < nunits; ++u) {
+        if (gain) gain[u] = nan;
+        if (reduction) reduction[u] = nan;
+    }
+    // live units by dim S = min(n_u, J): LDS kernels for <= 32 / 64 / 128, global scratch beyond
+    const int Dbin[4] = {32, 64, fsnap::JOINT_MAX_LDS_D, 0};
+    std::vector<int32_t> lists[4];
+    int64_t dmax = 0;
+    for (int64_t u = 0; u < nunits; ++u) {
+        if (!ctx->joint_halive[(size_t)u]) continue;
+        const int64_t d = std::min(ctx->joint_hoff[(size_t)u + 1] - ctx->joint_hoff[(size_t)u], J);
+        const int b = d <= 32 ? 0 : d <= 64 ? 1 : d <= fsnap::JOINT_MAX_LDS_D ? 2 : 3;
+        lists[b].push_back((int32_t)u);
+        if (b == 3) dmax = std::max(dmax, d);
+    }
+    ctx->joint_hlist.clear();
+    for (auto& l : lists) ctx->joint_hlist.insert(ctx->joint_hlist.end(), l.begin(), l.end());
+    if (ctx->joint_hlist.empty() || npos == 0) return FSNAP_OK;
+    if ((rc = check_rows(ctx))) return rc;
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    // [M | M B], zero-padded to 16-multiples; M B on the host in index order (K J r flops)
+    const int64_t Kp = (K + 15) / 16 * 16, Jp = (J + 15) / 16 * 16, rp = (r + 15) / 16 * 16, Wp = Jp + rp;
+    ctx->joint_hF.assign((size_t)(Kp * Wp), 0.0);
+    for (int64_t k = 0; k < K; ++k) {
+        double* row = &ctx->joint_hF[(size_t)(k * Wp)];
+        std::memcpy(row, M + k * J, (size_t)J * 8);
+        for (int64_t j = 0; j < J; ++j) {
+            const double mkj = M[k * J + j];
+            const double* bj = B + j * r;
+            for (int64_t c = 0; c < r; ++c) row[Jp + c] += mkj * bj[c];
+        }
+    }
+    ctx->joint_hB.assign((size_t)std::max<int64_t>(Jp * rp, 1), 0.0);
+    for (int64_t j = 0; j < J && r > 0; ++j) std::memcpy(&ctx->joint_hB[(size_t)(j * rp)], B + j * r, (size_t)r * 8);
+    const int nblk_lds = std::max(1, 16 * ctx->num_cu);
+    int nblk[4];
+    for (int b = 0; b < 3; ++b) nblk[b] = (int)std::min<int64_t>((int64_t)lists[b].size(), nblk_lds);
+    const int64_t sslice = dmax * dmax + dmax, yslice = fsnap::joint_yslice(dmax);
+    nblk[3] = lists[3].empty() ? 0
+                               : (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)lists[3].size(), 2 * (int64_t)ctx->num_cu,
+                                                                              (int64_t)(1 << 27) / std::max<int64_t>(sslice + yslice, 1)}));
+    if (!ctx->joint_F.ensure((size_t)(Kp * Wp) * 8) || !ctx->joint_B.ensure(ctx->joint_hB.size() * 8) ||
+        !ctx->joint_ZP.ensure((size_t)npos * (size_t)Wp * 8) || !ctx->joint_list.ensure(ctx->joint_hlist.size() * 4) ||
+        !ctx->joint_out.ensure((size_t)nunits * 2 * 8) || !ctx->joint_info.ensure((size_t)nunits * 4 * 8) ||
+        (nblk[3] > 0 && (!ctx->joint_S.ensure((size_t)nblk[3] * (size_t)sslice * 8) || !ctx->joint_Y.ensure((size_t)nblk[3] * (size_t)yslice * 8))))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(joint) failed");
+    FSNAP_HIP(hipMemcpyAsync(ctx->joint_F.p, ctx->joint_hF.data(), (size_t)(Kp * Wp) * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(F)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->joint_B.p, ctx->joint_hB.data(), ctx->joint_hB.size() * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(B)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->joint_list.p, ctx->joint_hlist.data(), ctx->joint_hlist.size() * 4, hipMemcpyHostToDevice, ctx->stream),
+              "hipMemcpy(lists)");
+    FSNAP_HIP(hipMemsetAsync(ctx->joint_out.p, 0xFF, (size_t)nunits * 16, ctx->stream), "hipMemset(out)");      // all-ones: NaN
+    FSNAP_HIP(hipMemsetAsync(ctx->joint_info.p, 0xFF, (size_t)nunits * 32, ctx->stream), "hipMemset(info)");
+    FSNAP_HIP(fsnap::launch_joint_rows(ctx->dA, ctx->lda, (int)K, (const int*)ctx->joint_idx.p, npos, (const double*)ctx->joint_om.p,
+                                       (const double*)ctx->joint_F.p, (int)Wp, (double*)ctx->joint_ZP.p, ctx->stream),
+              "launch fsnap_joint_rows_k");
+    size_t first = 0;
+    for (int b = 0; b < 4; ++b) {
+        const int ncl = (int)lists[b].size();
+        if (ncl > 0)
+            FSNAP_HIP(fsnap::launch_joint_units(Dbin[b], nblk[b], (const double*)ctx->joint_ZP.p, (int)Wp, (int)Jp, (int)J, (int)rp,
+                                                (const double*)ctx->joint_B.p, tau, (const int64_t*)ctx->joint_off.p,
+                                                (const int*)ctx->joint_list.p + first, ncl, (double*)ctx->joint_S.p, (int)dmax,
+                                                (double*)ctx->joint_Y.p, (double*)ctx->joint_out.p, (double*)ctx->joint_info.p,
+                                                ctx->stream),
+                      "launch fsnap_joint_unit_k");
+        first += (size_t)ncl;
+    }
+    ctx->joint_hout.resize((size_t)nunits * 2);
+    ctx->joint_hinfo.resize((size_t)nunits * 4);
+    FSNAP_HIP(hipMemcpyAsync(ctx->joint_hout.data(), ctx->joint_out.p, (size_t)nunits * 16, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(out)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->joint_hinfo.data(), ctx->joint_info.p, (size_t)nunits * 32, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(info)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    for (int64_t u = 0; u < nunits; ++u) {
+        if (!ctx->joint_halive[(size_t)u]) continue;
+        if (gain) gain[u] = ctx->joint_hout[(size_t)(2 * u)];
+        if (reduction) reduction[u] = ctx->joint_hout[(size_t)(2 * u + 1)];
+        if (info) std::memcpy(info + 4 * u, &ctx->joint_hinfo[(size_t)(4 * u)], 32);
+    }
+    return FSNAP_OK;
+}
+
+int fsnap_joint_retire(fsnap_ctx* ctx, int64_t unit) {
+    if (!ctx) return FSNAP_E_ARG;
+    int rc = joint_session(ctx, "fsnap_joint_retire");
+    if (rc) return rc;
+    if (unit < 0 || unit >= ctx->joint_nunits || !ctx->joint_halive[(size_t)unit])
+        return ctx->fail(FSNAP_E_ARG, "fsnap_joint_retire: unit %lld is not alive", (long long)unit);
+    ctx->joint_halive[(size_t)unit] = 0;
+    return FSNAP_OK;
+}
+
+int fsnap_joint_end(fsnap_ctx* ctx) {
+    if (!ctx) return FSNAP_E_ARG;
+    ctx->joint_active = false;
     return FSNAP_OK;
 }

@@ -140,6 +140,17 @@ struct fsnap_ctx {
     DevBuf loco_M, loco_idx, loco_off, loco_list, loco_Z, loco_aux, loco_pred, loco_info, loco_v, loco_H;
     std::vector<double> loco_hM, loco_hinfo;
     std::vector<int32_t> loco_hlist;
+    // fsnap_joint_*: the session's unit-sorted row index, unit offsets and per-position weights (uploaded once by begin), the
+    // padded factor [M | M B] and B, Z / Pi per position (npos x Wp), the bucketed list of live units, per-unit (gain, reduction)
+    // and info, per-workgroup scratch (S and the right-hand-side fragments of units too large for LDS); the host keeps the
+    // offsets and live flags.  joint_active is cleared by everything that changes the rows (cand_forget).
+    DevBuf joint_idx, joint_off, joint_om, joint_F, joint_B, joint_ZP, joint_list, joint_out, joint_info, joint_S, joint_Y;
+    std::vector<double> joint_hF, joint_hB, joint_hout, joint_hinfo;
+    std::vector<int64_t> joint_hoff;
+    std::vector<int32_t> joint_hlist;
+    std::vector<unsigned char> joint_halive;
+    bool joint_active = false;
+    int64_t joint_m = 0, joint_npos = 0, joint_nunits = 0;
     double* pinned = nullptr;                     // page-locked host staging of the packed statistics: plain (coarse-grained)
                                                   // pinned memory, the target of DMA copies only -- copies into COHERENT
                                                   // host memory were bimodal (2 MB in 0.05 or in 8 ms)

@@ -237,6 +237,22 @@ hipError_t launch_loco_cfg(int D, int nblocks, const double* Z, int Jp, int J, c
                            const double* pb, const int* idx, const int64_t* off, const int* clist, int ncl, double* Hg,
                            int dmax, double* vg, double* pred, double* info, hipStream_t st);
 
+// Joint unit scores (fsnap_joint.hip).  Kernel J1: for the npos positions of the unit-sorted row index idx,
+// ZP[p] = om[p] a_idx[p] [M | M B] (Wp doubles per position; Fp: device, Kp x Wp row-major, zero-padded: columns [0, Jp) the
+// factor M, columns [Jp, Wp) the target block M B; Wp = Jp without a target; om: the weight of every position).
+hipError_t launch_joint_rows(const double* A, int64_t lda, int K, const int* idx, int64_t npos, const double* om,
+                             const double* Fp, int Wp, double* ZP, hipStream_t st);
+// Kernel J2 for the ncl units of ulist (D = 32 / 64 / 128: S in LDS for dim S = min(n_u, J) <= D; D = 0: S in a slice of
+// dmax * dmax doubles of Sg per workgroup, the right-hand-side fragments in JOINT_YSLICE(dmax) doubles of Yg per workgroup):
+// S = I + Z Z^T / tau (n_u <= J) or I + Z^T Z / tau = L L^T; out[2 u] = gain = sum log L_ii; out[2 u + 1] = reduction (only
+// with rp > 0) = ||L^-1 Pi||_F^2 / tau (n space; Pi = columns [Jp, Jp + rp) of ZP) or ||B||_F^2 - ||L^-1 B||_F^2 (J space; Bp:
+// device, Jp x rp row-major, zero-padded); info[4 u ..] = (dim S, n space 1 / 0, smallest pivot, n_u).
+constexpr int JOINT_MAX_LDS_D = 128;
+constexpr int64_t joint_yslice(int64_t dmax) { return 4 * ((dmax + 15) / 16) * 4 * 64; }
+hipError_t launch_joint_units(int D, int nblocks, const double* ZP, int Wp, int Jp, int J, int rp, const double* Bp, double tau,
+                              const int64_t* off, const int* ulist, int ncl, double* Sg, int dmax, double* Yg, double* out,
+                              double* info, hipStream_t st);
+
 // Row-space solve (fsnap_trsm.hip).  Q <- X R^-1 by blocked substitution over the columns, one wave per 64 rows:
 // first pass X = diag(w_eff) A (src = A, leading dimension lds, per-row pairs wpack = (w_eff, w_eff b); rows with
 // w_eff = 0 become zero rows), later passes X = Q in place (src = Q, wpack = nullptr).  R: device, K16 x K16 row-major

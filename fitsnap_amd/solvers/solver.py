@@ -25,7 +25,7 @@ import numpy as np
 
 from .. import _capi
 from .._hostblas import blas_threads
-from . import loco, select, uq
+from . import loco, select, select_joint, uq
 
 
 class _TrainWeights:
@@ -1099,6 +1099,36 @@ class Solver:
         fewer than ``batch_size`` picks when the pool has fewer units.  Raises ValueError without a covariance or a noise
         variance."""
         return select.select_batch(self, batch_size, a, w, categories, row_scale, objective, noise, cov)
+
+    # ------------------------------------------------------------------------------
+    # joint unit scores: information gain and target-variance reduction (solvers/select_joint.py, csrc/fsnap_joint.hip)
+    # ------------------------------------------------------------------------------
+    def unit_scores(self, a=None, w=None, categories=None, criteria=("gain", "reduction"), target=None, row_scale=None,
+                    unit_cost=None, noise=None, cov=None):
+        """Joint scores of every unit of a pool under the posterior, exact for a linear model, without labels or refits:
+        "gain", the information the unit's labels carry, 1/2 logdet(I + X C X^T / noise) over ALL its weighted rows X at once
+        (correlated rows are not counted twice), and "reduction", the drop of the total predictive variance over a target
+        set, tr(T C) - tr(T C') (integrated-variance criterion) -- the two criteria that the reference's k-means clustering
+        (bayesian_active_learning.py:283-363) stands in for.
+
+        ``a``, ``w``, ``categories`` (required: the units), ``noise`` and ``cov`` as in ``select_batch``.  ``target``: None
+        = the pool rows themselves, weighted by ``row_scale``; an array of target rows, or ``(rows, scale)``; or
+        ``("gram", T)`` with T = sum s_j t_j t_j^T (K x K).  ``unit_cost``: one positive cost per unit (in key order) that
+        divides its scores.  Collective on several ranks (every unit on one rank; targets given as rows are this rank's
+        share, a Gram is rank 0's).  Returns a dict: "keys", "count" (rows per unit), "gain", "reduction" (None where not
+        asked for; an empty unit scores 0), "dims" (order of each unit's Cholesky factor) and "total" = tr(T C).  Raises
+        ValueError without a covariance or a noise variance, for an unknown criterion, a target of the wrong width and a
+        cost or noise that is not positive."""
+        return select_joint.unit_scores(self, a, w, categories, criteria, target, row_scale, unit_cost, noise, cov)
+
+    def select_units(self, batch_size, a=None, w=None, categories=None, criterion="gain", target=None, row_scale=None,
+                     unit_cost=None, noise=None, cov=None):
+        """Pick ``batch_size`` units one after the other by a JOINT criterion, "gain" or "reduction" (``unit_scores``), each
+        against the posterior that already contains the units picked before it: after a pick the covariance is downdated
+        as in ``select_batch`` and every live unit is scored again on the GPU.  Arguments as in ``unit_scores``; ties go to
+        the first key in rank-major key order.  Returns ``select_joint.UnitSelection(keys, scores, all_keys,
+        initial_scores, cov, dims)``; fewer than ``batch_size`` picks when the pool has fewer units."""
+        return select_joint.select_units(self, batch_size, a, w, categories, criterion, target, row_scale, unit_cost, noise, cov)
 
     # ------------------------------------------------------------------------------
     # leave-one-configuration-out errors (solvers/loco.py, csrc/fsnap_loco.hip)

@@ -364,6 +364,38 @@ int fsnap_select_end(fsnap_ctx* ctx);
 int fsnap_loco_rows(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, const double* beta, const int32_t* sorted_rows,
                     const int64_t* cfg_offsets, int64_t ncfg, double* pred_out, double* cfg_info_out);
 
+/* Joint scores of units (normally configurations) of the resident rows for active learning (kernels J1, J2 of
+ * csrc/fsnap_joint.hip, fp64 MFMA; the host algebra is solvers/select_joint.py).  With the posterior C = M M^T (M: K x J),
+ * the noise variance tau of a unit-weight row, the weighted rows X_u = diag(omega) A_u (n_u x K) of unit u, Z = X_u M and a
+ * target T = R^T R given as B = M^T R^T (J x r):
+ *     S = I + Z Z^T / tau (n_u <= J, "n space")  or  I + Z^T Z / tau (n_u > J, "J space")  = L L^T
+ *     gain_u      = 1/2 logdet(I + X_u C X_u^T / tau) = sum log L_ii           (the information the unit's labels carry)
+ *     reduction_u = tr(T C) - tr(T C'_u) = ||L^-1 Z B||_F^2 / tau  (n space)  =  ||B||_F^2 - ||L^-1 B||_F^2  (J space)
+ * (C'_u: the posterior with the unit added; no labels, no refit).  A session, like fsnap_select_*:
+ *   fsnap_joint_begin    sorted_rows[unit_offsets[nunits]] (host, int32) lists the rows of unit u at positions
+ *                        unit_offsets[u] ... unit_offsets[u + 1] - 1 (host, int64, unit_offsets[0] = 0, non-decreasing; every
+ *                        row at most once); omega (host, m doubles by row, NULL = 1) the weight of every row.  All of it is
+ *                        uploaded once; nothing of size O(m) crosses the bus afterwards.  Every unit with at least one row
+ *                        starts alive.  A running session is replaced.
+ *   fsnap_joint_score    M (host, K x J row-major), B (host, J x r row-major; NULL / r = 0: no target), tau > 0.  gain,
+ *                        reduction (host, nunits doubles; either may be NULL, reduction needs B): the scores of the live
+ *                        units, NaN for the others.  info (host, nunits x 4 doubles, may be NULL): dim S = min(n_u, J),
+ *                        n space 1 / 0, the smallest Cholesky pivot of S (>= 1 in exact arithmetic), n_u; written for live
+ *                        units only.  dim S <= 128 is factorised in LDS, larger ones through global scratch (untuned).
+ *   fsnap_joint_retire   takes a live unit out of the session (FSNAP_E_ARG when it is not alive).
+ *   fsnap_joint_end      drops the session.
+ * Whatever ends a selection session (fsnap_upload_rows, fsnap_bind_rows, fsnap_rows_alloc, fsnap_drop_rows, fsnap_assemble,
+ * fsnap_cat_prepare) ends this one: score and retire then return FSNAP_E_ARG, as they do without a session.  K must equal
+ * the resident rows' width.  With no rows (m = 0) or no live unit, score writes NaN and does nothing else.  Every sum runs in
+ * a fixed order that depends on the unit's own rows only: a unit's scores are bit-identical run to run and under any
+ * permutation or subset of the units.  No atomics.  Host in and out, synchronous. */
+int fsnap_joint_begin(fsnap_ctx* ctx, const int32_t* sorted_rows, const int64_t* unit_offsets, int64_t nunits,
+                      const double* omega);
+int fsnap_joint_score(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, int64_t r, const double* B, double tau,
+                      double* gain, double* reduction, double* info);
+int fsnap_joint_retire(fsnap_ctx* ctx, int64_t unit);
+int fsnap_joint_end(fsnap_ctx* ctx);
+
 /* ---- K x K solve (host side, no context needed) ----------------------------------- */
 
 /* Solve the K x K system given the statistics.  `kind` is one of FSNAP_SOLVE_*;
