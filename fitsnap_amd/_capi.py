@@ -123,6 +123,8 @@ SIGNATURES = {
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fsnap_loco_rows": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                 c_void_p]),
+    "fsnap_ridge_path": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
+                                 c_int64, c_void_p, c_void_p, c_void_p]),
     "fsnap_select_begin": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int]),
     "fsnap_select_pick": (c_int, [c_void_p, c_int, POINTER(ctypes.c_int32), POINTER(c_double)]),
     "fsnap_select_retire": (c_int, [c_void_p, ctypes.c_int32]),
@@ -975,6 +977,39 @@ class HipContext:
         self._check(self._lib.fsnap_loco_rows(self._h, K, J, _ptr(M), _ptr(beta), _ptr(rows) if rows.size else None,
                                               _ptr(off), ncfg, _ptr(pred), _ptr(info)))
         return pred, info
+
+    def ridge_path(self, G, c, alphas, sorted_rows, unit_offsets, row_class, nclass, want_preds=False):
+        """Leave-one-unit-out refits of the resident training rows over a grid of alphas (``fsnap_ridge_path``, K <= 144): the
+        statistics G (K x K), c (K), the grid ``alphas`` (Q), the rows of unit u at
+        ``sorted_rows[unit_offsets[u]:unit_offsets[u + 1]]``, ``row_class`` (m, uint8, < nclass <= 8).  Returns (sums
+        (Q x nunits x nclass x 4: n, sum |r|, sum r^2, sum (w r)^2), info (Q x nunits x 2: smallest pivot, identifiable),
+        preds (Q x m, NaN where a row is not listed or its unit is not identifiable; None without ``want_preds``))."""
+        G = _f64(G, "G")
+        if G.ndim != 2 or G.shape[0] != G.shape[1]:
+            raise ValueError("G must be square")
+        K = G.shape[0]
+        c = _f64(c, "c").reshape(-1)
+        if c.shape != (K,):
+            raise ValueError(f"c has shape {c.shape}, expected ({K},)")
+        alphas = _f64(alphas, "alphas").reshape(-1)
+        rows = np.ascontiguousarray(sorted_rows, dtype=np.int32).reshape(-1)
+        off = np.ascontiguousarray(unit_offsets, dtype=np.int64).reshape(-1)
+        if off.size < 1:
+            raise ValueError("unit_offsets needs nunits + 1 entries")
+        nunits = off.size - 1
+        if off[-1] != rows.size:
+            raise ValueError(f"unit_offsets ends at {off[-1]}, sorted_rows has {rows.size} entries")
+        cls = np.ascontiguousarray(row_class, dtype=np.uint8).reshape(-1)
+        if cls.size != self.m:
+            raise ValueError(f"row_class has {cls.size} entries for {self.m} rows")
+        Q, nclass = alphas.size, int(nclass)
+        sums = np.empty((Q, nunits, max(nclass, 0), 4))
+        info = np.empty((Q, nunits, 2))
+        preds = np.empty((Q, self.m)) if want_preds else None
+        self._check(self._lib.fsnap_ridge_path(self._h, K, _ptr(G), _ptr(c), _ptr(alphas), Q, _ptr(rows) if rows.size else None,
+                                               _ptr(off), nunits, _ptr(cls) if cls.size else None, nclass, _ptr(sums),
+                                               _ptr(info), _ptr(preds) if want_preds else None))
+        return sums, info, preds
 
     def lstsq_rows(self, rcond: float, K: int = None):
         """``lstsq(aw, bw, rcond)`` of the resident rows computed on the rows (fsnap_lstsq_rows); collective when the

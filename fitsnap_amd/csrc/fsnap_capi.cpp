@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <atomic>
 #include <chrono>
 #include <cstdarg>
@@ -2756,6 +2757,97 @@ int fsnap_loco_rows(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, const
     FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
     for (int64_t c = 0; c < ncfg; ++c)
         if (cfg_offsets[c + 1] > cfg_offsets[c]) std::memcpy(cfg_info_out + 4 * c, &ctx->loco_hinfo[(size_t)(4 * c)], 32);
+    return FSNAP_OK;
+}
+
+// ---- leave-one-unit-out refits over a grid of alphas (kernel P1 of fsnap_path.hip) ---------------------------------------
+
+int fsnap_ridge_path(fsnap_ctx* ctx, int64_t K, const double* G, const double* c, const double* alphas, int64_t Q,
+                     const int32_t* sorted_rows, const int64_t* unit_offsets, int64_t nunits, const uint8_t* row_class,
+                     int64_t nclass, double* sums_out, double* info_out, double* pred_out) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_ridge_path";
+    if (!G || !c || !alphas || !unit_offsets || !sums_out || !info_out) return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
+    if (K < 1 || K > fsnap::PATH_MAX_K)
+        return ctx->fail(FSNAP_E_ARG, "%s: K = %lld (1 ... %d)", who, (long long)K, fsnap::PATH_MAX_K);
+    if (Q < 1 || Q > 0xFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: Q = %lld", who, (long long)Q);
+    for (int64_t q = 0; q < Q; ++q)
+        if (!std::isfinite(alphas[q]) || alphas[q] < 0.0)
+            return ctx->fail(FSNAP_E_ARG, "%s: alphas[%lld] = %g is negative or not finite", who, (long long)q, alphas[q]);
+    if (nclass < 1 || nclass > fsnap::PATH_MAX_CLASS)
+        return ctx->fail(FSNAP_E_ARG, "%s: nclass = %lld (1 ... %d)", who, (long long)nclass, fsnap::PATH_MAX_CLASS);
+    if (nunits < 0 || nunits > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: nunits = %lld", who, (long long)nunits);
+    const int64_t m = ctx->m;
+    if (m > 0 && K != ctx->K)
+        return ctx->fail(FSNAP_E_ARG, "%s: K = %lld, the resident rows have %lld columns", who, (long long)K, (long long)ctx->K);
+    if (m > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: needs m < 2^31", who);
+    if (unit_offsets[0] != 0) return ctx->fail(FSNAP_E_ARG, "%s: unit_offsets[0] = %lld", who, (long long)unit_offsets[0]);
+    for (int64_t u = 0; u < nunits; ++u)
+        if (unit_offsets[u + 1] < unit_offsets[u])
+            return ctx->fail(FSNAP_E_ARG, "%s: unit_offsets decrease at %lld", who, (long long)u);
+    const int64_t npos = unit_offsets[nunits];
+    if (npos > m) return ctx->fail(FSNAP_E_ARG, "%s: %lld positions for %lld rows", who, (long long)npos, (long long)m);
+    if (npos > 0 && (!sorted_rows || !row_class)) return ctx->fail(FSNAP_E_ARG, "%s: sorted_rows / row_class is NULL", who);
+    {   // every position names a distinct row of the context and a class below nclass
+        std::vector<unsigned char> seen((size_t)std::max<int64_t>(m, 1), 0);
+        for (int64_t p = 0; p < npos; ++p) {
+            const int32_t r = sorted_rows[p];
+            if (r < 0 || r >= m || seen[(size_t)r])
+                return ctx->fail(FSNAP_E_ARG, "%s: sorted_rows[%lld] = %d is out of range or repeated", who, (long long)p, r);
+            seen[(size_t)r] = 1;
+            if (row_class[r] >= nclass)
+                return ctx->fail(FSNAP_E_ARG, "%s: row %d has class %d, nclass = %lld", who, r, (int)row_class[r], (long long)nclass);
+        }
+    }
+    const size_t nsum = (size_t)Q * (size_t)nunits * (size_t)nclass * 4, ninfo = (size_t)Q * (size_t)nunits * 2;
+    if (npos == 0) {                              // no rows at all: every unit is empty, nothing to leave out
+        std::fill(sums_out, sums_out + nsum, 0.0);
+        for (size_t i = 0; i < ninfo; i += 2) {
+            info_out[i] = std::numeric_limits<double>::infinity();
+            info_out[i + 1] = 1.0;
+        }
+        if (pred_out) std::fill(pred_out, pred_out + (size_t)Q * (size_t)m, std::numeric_limits<double>::quiet_NaN());
+        return FSNAP_OK;
+    }
+    int rc;
+    if ((rc = check_rows(ctx)) || (rc = check_weights(ctx))) return rc;
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    if (ctx->uq_inflight) {
+        FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+        ctx->uq_inflight = false;
+    }
+    int npk = 0;
+    if ((rc = ensure_wpack(ctx, &npk))) return rc;
+    const double* wpack = ctx->wpack_override ? ctx->wpack_override : (const double*)ctx->wpack.p;
+    const int nblocks = (int)std::min<int64_t>(nunits, (int64_t)fsnap::path_blocks_per_cu((int)K) * std::max(1, ctx->num_cu));
+    const size_t nin = (size_t)(K * K + K + Q);
+    if (!ctx->path_in.ensure(nin * 8) || !ctx->path_cls.ensure((size_t)m) || !ctx->loco_idx.ensure((size_t)npos * 4) ||
+        !ctx->loco_off.ensure((size_t)(nunits + 1) * 8) ||
+        !ctx->path_base.ensure((size_t)nblocks * fsnap::path_base_doubles((int)K) * 8) || !ctx->path_sums.ensure(nsum * 8) ||
+        !ctx->path_info.ensure(ninfo * 8) || (pred_out && !ctx->path_pred.ensure((size_t)Q * (size_t)m * 8)))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(ridge path) failed");
+    double* din = (double*)ctx->path_in.p;
+    FSNAP_HIP(hipMemcpyAsync(din, G, (size_t)(K * K) * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(G)");
+    FSNAP_HIP(hipMemcpyAsync(din + K * K, c, (size_t)K * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(c)");
+    FSNAP_HIP(hipMemcpyAsync(din + K * K + K, alphas, (size_t)Q * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(alphas)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->path_cls.p, row_class, (size_t)m, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(classes)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->loco_idx.p, sorted_rows, (size_t)npos * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(idx)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->loco_off.p, unit_offsets, (size_t)(nunits + 1) * 8, hipMemcpyHostToDevice, ctx->stream),
+              "hipMemcpy(offsets)");
+    // the kernel writes every entry of sums and info (units without rows: zero sums, info (inf, 1))
+    if (pred_out) FSNAP_HIP(hipMemsetAsync(ctx->path_pred.p, 0xFF, (size_t)Q * (size_t)m * 8, ctx->stream), "hipMemset(pred)");
+    FSNAP_HIP(fsnap::launch_ridge_path(nblocks, ctx->dA, ctx->lda, (int)K, wpack, ctx->db, (const int*)ctx->loco_idx.p,
+                                       (const int64_t*)ctx->loco_off.p, (int)nunits, din, din + K * K, din + K * K + K, (int)Q,
+                                       (const unsigned char*)ctx->path_cls.p, (int)nclass, (double*)ctx->path_base.p,
+                                       (double*)ctx->path_sums.p, (double*)ctx->path_info.p,
+                                       pred_out ? (double*)ctx->path_pred.p : nullptr, m, ctx->stream),
+              "launch fsnap_path_k");
+    FSNAP_HIP(hipMemcpyAsync(sums_out, ctx->path_sums.p, nsum * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(sums)");
+    FSNAP_HIP(hipMemcpyAsync(info_out, ctx->path_info.p, ninfo * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(info)");
+    if (pred_out)
+        FSNAP_HIP(hipMemcpyAsync(pred_out, ctx->path_pred.p, (size_t)Q * (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream),
+                  "hipMemcpy(pred)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
     return FSNAP_OK;
 }
 

@@ -237,6 +237,22 @@ hipError_t launch_loco_cfg(int D, int nblocks, const double* Z, int Jp, int J, c
                            const double* pb, const int* idx, const int64_t* off, const int* clist, int ncl, double* Hg,
                            int dmax, double* vg, double* pred, double* info, hipStream_t st);
 
+// Leave-one-unit-out refits over a grid of alphas (fsnap_path.hip, kernel P1; K <= PATH_MAX_K).  For every unit u (positions
+// off[u] .. off[u + 1] of idx) and alpha_q: beta = (G - G_u + alpha_q I)^-1 (c - c_u) by a Jacobi-scaled blocked Cholesky,
+// sums[((q nunits + u) nclass + cls) 4 ..] = (n, sum |r|, sum r^2, sum (w r)^2) of r_i = b_i - a_i . beta over the unit's rows
+// of class rcls[row] = cls, info[(q nunits + u) 2 ..] = (smallest pivot, identifiable 1 / 0), pred[q m + row] = a_i . beta
+// (pred may be nullptr; NaN for a unit that is not identifiable at alpha_q).  Units without rows get zero sums and info (inf, 1).  G, c,
+// alphas: device.  Bg: nblocks x path_base_doubles(K) doubles of scratch.
+constexpr int PATH_MAX_K = 144;
+constexpr int PATH_QCHUNK = 16;
+constexpr int PATH_MAX_CLASS = 8;
+inline size_t path_base_doubles(int K) { return (size_t)((K + 15) / 16) * (size_t)((K + 15) / 16 + 1) / 2 * 256; }
+int path_blocks_per_cu(int K);
+hipError_t launch_ridge_path(int nblocks, const double* A, int64_t lda, int K, const double* wpack, const double* b,
+                             const int* idx, const int64_t* off, int nunits, const double* G, const double* c,
+                             const double* alphas, int Q, const unsigned char* rcls, int nclass, double* Bg, double* sums,
+                             double* info, double* pred, int64_t m, hipStream_t st);
+
 // Joint unit scores (fsnap_joint.hip).  Kernel J1: for the npos positions of the unit-sorted row index idx,
 // ZP[p] = om[p] a_idx[p] [M | M B] (Wp doubles per position; Fp: device, Kp x Wp row-major, zero-padded: columns [0, Jp) the
 // factor M, columns [Jp, Wp) the target block M B; Wp = Jp without a target; om: the weight of every position).

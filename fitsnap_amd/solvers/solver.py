@@ -25,7 +25,7 @@ import numpy as np
 
 from .. import _capi
 from .._hostblas import blas_threads
-from . import loco, select, select_joint, uq
+from . import loco, ridge_path, select, select_joint, uq
 
 
 class _TrainWeights:
@@ -1147,3 +1147,22 @@ class Solver:
         max |LOO residual|, identifiable, d, smallest pivot) and the number of units that are not identifiable.
         Raises ValueError for solvers whose fit is not a linear smoother of the rows and for ``apply_transpose``."""
         return loco.loco_errors(self, by, fs_dict, b, w)
+
+    # ------------------------------------------------------------------------------
+    # leave-one-configuration-out error over a grid of ridge alphas (solvers/ridge_path.py, csrc/fsnap_path.hip)
+    # ------------------------------------------------------------------------------
+    def ridge_path(self, alphas, by="Configs", fs_dict=None, b=None, w=None, method="auto", want_preds=False):
+        """Exact leave-one-unit-out error of the ridge fit (G + alpha I) beta = c as a function of alpha, after
+        ``perform_fit`` of a RIDGE or SVD solver, on the GPU from the resident training rows and the statistics of the fit:
+        for every unit (``fs_dict[by]``, as in ``loco_errors``) and every alpha of the grid, the rows of the unit are
+        predicted by the refit without them.  ``method``: "refit" (the fused kernel, K <= 144), "woodbury" (per alpha a
+        factor and a ``fsnap_loco_rows`` pass) or "auto" (the kernel where it exists).  Labels, truths and weights as in
+        ``loco_errors``.  Collective on several ranks; every unit must live on one rank.  Returns ``RidgePath(alphas, fits,
+        table, units, unidentifiable, best, best_alpha, preds)``: the Q x K fits on all rows (rank 0), a DataFrame indexed
+        (alpha, Row_Type, with an ``*ALL`` row) of ncount / mae / rmse / w_rmse of the LOO residuals over identifiable units,
+        a DataFrame with one row per (alpha, unit), the count of units that are not identifiable per alpha, the index and
+        value of the alpha with the smallest total weighted LOO SSE (alphas with a unit that is not identifiable are not
+        eligible; ties go to the smaller alpha) and, with ``want_preds``, the Q x m LOO predictions.  Neither the fit nor the
+        config is changed: write ``best_alpha`` into ``[RIDGE] alpha`` and fit.  Raises ValueError for other solvers, for
+        ``apply_transpose``, for an SVD fit that took the row-space path and for rows that are not those of the fit."""
+        return ridge_path.ridge_path(self, alphas, by, fs_dict, b, w, method, want_preds)

@@ -364,6 +364,26 @@ int fsnap_select_end(fsnap_ctx* ctx);
 int fsnap_loco_rows(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, const double* beta, const int32_t* sorted_rows,
                     const int64_t* cfg_offsets, int64_t ncfg, double* pred_out, double* cfg_info_out);
 
+/* Exact leave-one-unit-out errors of ridge fits over a grid of alphas from the resident training rows (kernel P1 of
+ * csrc/fsnap_path.hip, fp64 MFMA; K <= 144).  G (host, K x K row-major; the lower triangle is read) and c (host, K) are the
+ * statistics of the weighted rows x_i = w_i a_i, y_i = w_i b_i (w_i = 0 off the mask), alphas (host, Q doubles, finite, >= 0)
+ * the grid.  sorted_rows[unit_offsets[nunits]] (host, int32) lists the rows of unit u at positions unit_offsets[u] ...
+ * unit_offsets[u + 1] - 1 (host, int64, unit_offsets[0] = 0, non-decreasing; every row at most once); row_class (host, m bytes
+ * by row) the class < nclass <= 8 of every listed row.  For every unit and alpha_q the REFIT without the unit's rows:
+ *     B = G - X_u^T X_u + alpha_q I,  D = sqrt(diag B),  beta = D^-1 (D^-1 B D^-1)^-1 D^-1 (c - X_u^T y_u)   (blocked Cholesky)
+ *     p_i = a_i . beta,  r_i = b_i - p_i     for every row i of u
+ * sums_out: Q x nunits x nclass x 4 doubles (n, sum |r|, sum r^2, sum (w r)^2 over the unit's rows of the class, in position
+ * order); info_out: Q x nunits x 2 doubles (smallest pivot of the scaled matrix, identifiable 1 / 0); pred_out (may be NULL):
+ * Q x m doubles, NaN for rows that are not listed.  A unit is not identifiable at alpha_q when a diagonal entry of B is <= 0
+ * (in floating point: <= 1e-10 (G_jj + alpha_q), the downdate has cancelled) or a pivot is <= 1e-10 (it is never divided
+ * through): its predictions are NaN and its sums zero.  A unit without rows has zero sums and info (inf, 1).  Uses the resident rows, b and weights.  FSNAP_E_ARG for K != the resident width, K > 144,
+ * Q < 1, a negative or non-finite alpha, nclass outside 1 ... 8, a class >= nclass.  Every sum runs in a fixed order that
+ * depends on the unit's own rows only: bit-identical run to run and under any permutation of the units; no atomics.  Host in
+ * and out, synchronous. */
+int fsnap_ridge_path(fsnap_ctx* ctx, int64_t K, const double* G, const double* c, const double* alphas, int64_t Q,
+                     const int32_t* sorted_rows, const int64_t* unit_offsets, int64_t nunits, const uint8_t* row_class,
+                     int64_t nclass, double* sums_out, double* info_out, double* pred_out);
+
 /* Joint scores of units (normally configurations) of the resident rows for active learning (kernels J1, J2 of
  * csrc/fsnap_joint.hip, fp64 MFMA; the host algebra is solvers/select_joint.py).  With the posterior C = M M^T (M: K x J),
  * the noise variance tau of a unit-weight row, the weighted rows X_u = diag(omega) A_u (n_u x K) of unit u, Z = X_u M and a
