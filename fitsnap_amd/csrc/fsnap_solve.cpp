@@ -24,6 +24,7 @@
 #include <cstdint>
 #include <cstring>
 #include <limits>
+#include <mutex>
 #include <thread>
 #include <vector>
 
@@ -330,6 +331,251 @@ void chol_solve(const double* u, int n, double* x) {
     chol_solve_inv(u, n, x, inv.data());
 }
 
+// ---- fused finish of a small fit: scaling, factorisation and forward sweep in ONE left-looking pass --------------
+// (48 <= n <= 256, n a multiple of 16, one thread: the range in which fast_chol runs chol_upper_rb with 8-row panels.)
+// The statistics were just written by the device, so every line of G is cold.  The right-looking factorisation needs the
+// whole scaled matrix at step 0, i.e. a pass of cold reads before any arithmetic; the left-looking order needs the rows
+// of ONE 8-row panel at a time, so G is consumed panel by panel, prefetched two panels ahead, and its reads hide under
+// the updates of the panels before.  Per panel: build its scaled rows, subtract the contributions of all earlier rows
+// k = 0 .. jb-1 (ascending, one fused multiply-subtract each, 8 rows x 16 columns in 16 accumulators), run the panel
+// recurrence of chol_panel while the block is still in registers, store.  The right-hand side z is one more column.
+//
+// Bit-identical to scale/build + chol_upper_rb(NBK = 8) + the forward sweep of chol_solve_inv: an element (i, c) starts
+// from the same scaled value, receives -u[k][i] * u[k][c] for k = 0 .. i-1 in ascending order as one FMA each
+// (unconditionally for rows of earlier panels, skipped for u[k][i] == 0 inside the panel, as there), and is then
+// square-rooted or multiplied by the same reciprocal; only the order BETWEEN elements differs.
+// Blocks are updated, scaled and stored in full, i.e. up to 15 entries left of the diagonal are touched too, and where the
+// panel starts in the second half of its diagonal block (jb = c0 + 8) the update reads earlier rows' entries left of THEIR
+// diagonals.  Such values only ever flow into other entries left of a diagonal: the multipliers u[k][i] (i > k), the z
+// column, the backward sweep and chol_solve all read strictly right of the diagonal.  Nothing may read what lies left of it.
+
+// (macros: an 8-wide vector cannot cross a function boundary of the AVX2 baseline, inlined or not)
+#define LD8(p) (*reinterpret_cast<const v8du*>(p))
+#define ST8(p, v) (*reinterpret_cast<v8du*>(p) = (v))
+#define BC8(f) (v8d{(f), (f), (f), (f), (f), (f), (f), (f)})
+
+// fetch rows [r0, r1) of G (the part the scaling pass reads: from the 8-block of the diagonal on) into L2
+FSNAP_INLINE void prefetch_g_rows(const double* G, int K, int r0, int r1) {
+    if (r1 > K) r1 = K;
+    for (int i = r0; i < r1; ++i) {
+        const double* gi = G + (size_t)i * K;
+        for (int j = i & ~7; j < K; j += 8) __builtin_prefetch(gi + j, 0, 2);
+    }
+}
+
+// Row i of the Jacobi-scaled matrix, built in 8-wide vectors from the vector that holds the diagonal: the < 8 entries left
+// of the diagonal receive (valid, unused) scaled values, everything further left is zeroed -- the blocked factorisations
+// update whole column chunks.  The finiteness of everything read is folded into chk0 / chk1 / chk.
+FSNAP_INLINE void scaled_row(const double* G, const double* dsc, int K, int Kp, int i, double alpha, bool upper_only,
+                             double* U, v8d& chk0, v8d& chk1, double& chk) {
+    const v8d zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    const double* gi = G + (size_t)i * K;
+    double* ui = U + (size_t)i * Kp;
+    const double di = dsc[i];
+    const v8d dv = {di, di, di, di, di, di, di, di};
+    const int j0 = i & ~7;
+    int j = 0;
+    for (; j + 8 <= j0; j += 8) *(v8du*)(ui + j) = zero;
+    if (upper_only && j + 8 <= K) {
+        // the vector that holds the diagonal: what lies left of it was never written by the device
+        typedef long long v8l __attribute__((vector_size(64)));
+        const v8l lanes = {0, 1, 2, 3, 4, 5, 6, 7};
+        const v8l keep = (lanes + (long long)j) >= (long long)i;
+        const v8d g0 = (v8d)((v8l)(*(const v8du*)(gi + j)) & keep);
+        chk0 += g0 * zero;
+        *(v8du*)(ui + j) = g0 * dv * *(const v8du*)(dsc + j);
+        j += 8;
+    }
+    for (; j + 16 <= K; j += 16) {
+        const v8d g0 = *(const v8du*)(gi + j), g1 = *(const v8du*)(gi + j + 8);
+        chk0 += g0 * zero;
+        chk1 += g1 * zero;
+        *(v8du*)(ui + j) = g0 * dv * *(const v8du*)(dsc + j);
+        *(v8du*)(ui + j + 8) = g1 * dv * *(const v8du*)(dsc + j + 8);
+    }
+    for (; j + 8 <= K; j += 8) {
+        const v8d g0 = *(const v8du*)(gi + j);
+        chk0 += g0 * zero;
+        *(v8du*)(ui + j) = g0 * dv * *(const v8du*)(dsc + j);
+    }
+    for (; j < K; ++j) {
+        const double gij = (upper_only && j < i) ? 0.0 : gi[j];
+        ui[j] = gij * di * dsc[j];
+        chk += gij * 0.0;
+    }
+    for (; j < Kp; ++j) ui[j] = 0.0;
+    ui[i] = (gi[i] + alpha) * di * di;
+}
+
+// rows [jb, jb + 8) x columns [c0, c0 + 16) of u, in 16 accumulators:  y -= sum_{k < jb} u[k][jb + r] * u[k][c0:c0+16]
+// (ascending k).  RHS: the same for the 8 right-hand-side entries z[jb : jb + 8] (the forward sweep of these rows).
+template <bool RHS>
+FSNAP_INLINE void left_update_8x16(const double* u, int n, int jb, int c0, v8d (&y)[16], double* z) {
+    v8d zv = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (RHS) zv = LD8(z + jb);
+    const double* uk = u;
+    for (int k = 0; k < jb; ++k, uk += n) {
+        const v8d u0 = LD8(uk + c0), u1 = LD8(uk + c0 + 8);
+        const double* f = uk + jb;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const v8d b = BC8(f[r]);
+            y[2 * r] -= b * u0;
+            y[2 * r + 1] -= b * u1;
+        }
+        if (RHS) {
+            const v8d zk = BC8(z[k]);
+            zv -= zk * LD8(f);
+        }
+    }
+    if (RHS) ST8(z + jb, zv);
+}
+
+// The 16-column block that holds the diagonal of panel [jb, jb + 8): earlier rows' contributions, then the recurrence
+// of chol_panel restricted to the block (pivot, reciprocal, row scaling, in-panel updates), the right-hand side along.
+// inv[0:8] receives the reciprocals of the pivots' roots.  Returns -1 or the failing row.
+FSNAP_INLINE int fused_diag_block(double* u, int n, int jb, double* z, double* inv, double* mp) {
+    const int c0 = jb & ~15, off = jb - c0;
+    double* blk = u + (size_t)jb * n + c0;
+    if (jb > 0) {
+        v8d y[16];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            y[2 * r] = LD8(blk + (size_t)r * n);
+            y[2 * r + 1] = LD8(blk + (size_t)r * n + 8);
+        }
+        left_update_8x16<true>(u, n, jb, c0, y, z);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            ST8(blk + (size_t)r * n, y[2 * r]);
+            ST8(blk + (size_t)r * n + 8, y[2 * r + 1]);
+        }
+    }
+    for (int j = 0; j < 8; ++j) {
+        double* uj = blk + (size_t)j * n;
+        const double d = uj[off + j];
+        if (d < *mp) *mp = d;
+        if (!(d > 0.0) || !std::isfinite(d)) return jb + j;
+        const double r = std::sqrt(d), iv = 1.0 / r;
+        inv[j] = iv;
+        const v8d ivv = BC8(iv);
+        const v8d s0 = LD8(uj) * ivv, s1 = LD8(uj + 8) * ivv;
+        ST8(uj, s0);
+        ST8(uj + 8, s1);
+        uj[off + j] = r;
+        const double zj = z[jb + j] * iv;
+        z[jb + j] = zj;
+        for (int i = j + 1; i < 8; ++i) {
+            const double f = uj[off + i];
+            z[jb + i] -= zj * f;
+            if (f != 0.0) {
+                double* ui = blk + (size_t)i * n;
+                const v8d fv = BC8(f);
+                v8d y0 = LD8(ui), y1 = LD8(ui + 8);
+                y0 -= fv * s0;
+                y1 -= fv * s1;
+                ST8(ui, y0);
+                ST8(ui + 8, y1);
+            }
+        }
+    }
+    return -1;
+}
+
+// a 16-column block right of the diagonal block: earlier rows' contributions and the panel recurrence in registers
+FSNAP_INLINE void fused_right_block(double* u, int n, int jb, int c0, const double* inv) {
+    double* blk = u + (size_t)jb * n + c0;
+    v8d y[16];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        y[2 * r] = LD8(blk + (size_t)r * n);
+        y[2 * r + 1] = LD8(blk + (size_t)r * n + 8);
+    }
+    left_update_8x16<false>(u, n, jb, c0, y, nullptr);
+    const double* fr = u + (size_t)jb * n + jb;      // fr[j * n + i] = u[jb + j][jb + i], final
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const v8d ivv = BC8(inv[j]);
+        y[2 * j] *= ivv;
+        y[2 * j + 1] *= ivv;
+#pragma unroll
+        for (int i = j + 1; i < 8; ++i) {
+            const double f = fr[(size_t)j * n + i];
+            if (f != 0.0) {
+                const v8d fv = BC8(f);
+                y[2 * i] -= fv * y[2 * j];
+                y[2 * i + 1] -= fv * y[2 * j + 1];
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        ST8(blk + (size_t)r * n, y[2 * r]);
+        ST8(blk + (size_t)r * n + 8, y[2 * r + 1]);
+    }
+}
+
+// G (K x K, upper triangle read; both triangles valid unless upper_only), dsc (Jacobi scaling, K entries) -> u (Kp x Kp:
+// the factor U of the scaled, identity-padded matrix), z (in: scaled right-hand side, zero-padded; out: U^-T z),
+// inv (1 / U[i][i]).  *chk_out is 0.0 when everything read was finite.  Returns -1 or the failing pivot.
+FSNAP_CLONES int fused_scale_chol(const double* G, const double* dsc, int K, int Kp, double alpha, bool upper_only,
+                                  double* u, double* z, double* inv, double* min_piv2, double* chk_out) {
+    const v8d zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    v8d chk0 = zero, chk1 = zero;
+    double chk = 0.0;
+    double mp = std::numeric_limits<double>::infinity();
+    int fail = -1;
+    for (int jb = 0; jb < Kp && fail < 0; jb += 8) {
+        prefetch_g_rows(G, K, jb + 16, jb + 24);        // (the caller fetched the first two panels)
+        for (int i = jb; i < jb + 8; ++i) {
+            if (i < K) {
+                scaled_row(G, dsc, K, Kp, i, alpha, upper_only, u, chk0, chk1, chk);
+            } else {                                    // identity block of the padding
+                double* ui = u + (size_t)i * Kp;
+                for (int j = 0; j < Kp; ++j) ui[j] = 0.0;
+                ui[i] = 1.0;
+            }
+        }
+        fail = fused_diag_block(u, Kp, jb, z, inv + jb, &mp);
+        if (fail >= 0) break;
+        for (int c0 = (jb & ~15) + 16; c0 < Kp; c0 += 16) fused_right_block(u, Kp, jb, c0, inv + jb);
+    }
+    const v8d cs = chk0 + chk1;
+    chk += ((cs[0] + cs[1]) + (cs[2] + cs[3])) + ((cs[4] + cs[5]) + (cs[6] + cs[7]));
+    *chk_out = chk;
+    *min_piv2 = mp;
+    return fail;
+}
+
+// dsc[i] = 1 / sqrt(d[i] + alpha), eight at a time (d == dsc is allowed); false when an entry is not positive and finite
+FSNAP_CLONES bool jacobi_scale(const double* d, int K, double alpha, double* dsc) {
+    typedef long long v8l __attribute__((vector_size(64)));
+    const v8d zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    const v8d av = BC8(alpha), one = BC8(1.0);
+    v8l good = {-1, -1, -1, -1, -1, -1, -1, -1};
+    int i = 0;
+    for (; i + 8 <= K; i += 8) {
+        const v8d g = LD8(d + i) + av;
+        good &= (g > zero) & (g - g == zero);
+        ST8(dsc + i, one / __builtin_elementwise_sqrt(g));
+    }
+    bool ok = (good[0] & good[1] & good[2] & good[3] & good[4] & good[5] & good[6] & good[7]) != 0;
+    for (; i < K; ++i) {
+        const double g = d[i] + alpha;
+        if (!(g > 0.0) || !std::isfinite(g)) ok = false;
+        dsc[i] = 1.0 / std::sqrt(g);
+    }
+    return ok;
+}
+
+// the backward sweep of chol_solve_inv alone (the fused pass has done the forward sweep and left the reciprocals)
+FSNAP_CLONES void chol_back_inv(const double* u, int n, double* x, const double* inv) {
+    for (int i = n - 1; i >= 0; --i) {
+        const double* r = u + (size_t)i * n;
+        x[i] = (x[i] - dotv(r + i + 1, x + i + 1, n - 1 - i)) * inv[i];
+    }
+}
+
 // LU with partial pivoting, solve a x = b (a destroyed).  Returns false if singular.
 bool lu_solve(double* a, int n, double* b) {
     std::vector<int> piv(n);
@@ -631,15 +877,30 @@ int chol_upper_rb_mt(double* a, int n, double* min_piv2, int NBK, int nt) {
 
 // factorisation used by the fast path; FSNAP_CHOL_VARIANT (environment, tests / tuning only) forces a variant:
 // 0 = auto, 1 = unblocked, 2 = 64-row panels + threads, 3 = register-blocked chunks
-int fast_chol(double* u, int n, double* mp2) {
+int chol_variant_env() {
     static const int forced = [] {
         const char* e = std::getenv("FSNAP_CHOL_VARIANT");
         return e ? std::atoi(e) : 0;
     }();
+    return forced;
+}
+int chol_nbk_env() {
     static const int nbk_env = [] {
         const char* e = std::getenv("FSNAP_CHOL_NBK");
         return e ? std::atoi(e) : 0;
     }();
+    return nbk_env;
+}
+
+// The fused finish (fused_scale_chol) replaces scale/build + fast_chol + forward sweep of the fast path where fast_chol
+// would run chol_upper_rb with 8-row panels on one thread: 48 <= n <= 256 (n / 160 < 2 keeps those on one thread whatever
+// FSNAP_CHOL_THREADS says).  Any non-zero FSNAP_CHOL_VARIANT, or a panel height forced by FSNAP_CHOL_NBK, keeps the
+// separate steps -- the reference the fused pass is bit-compared with.
+bool use_fused_finish(int n) { return chol_variant_env() == 0 && chol_nbk_env() <= 0 && n >= 48 && n <= 256 && (n & 15) == 0; }
+
+int fast_chol(double* u, int n, double* mp2) {
+    const int forced = chol_variant_env();
+    const int nbk_env = chol_nbk_env();
     if (forced == 1) return chol_upper(u, n, mp2);
     if (forced == 2) return chol_upper_blocked(u, n, mp2, 64);
     if (forced == 3 || n >= 48) {
@@ -678,15 +939,65 @@ int fast_chol(double* u, int n, double* mp2) {
 }  // namespace
 
 namespace {
-struct PhaseTimer {   // FSNAP_SOLVE_TIMING=1: print the phases of the fast path to stderr (tuning aid)
-    bool on;
+// FSNAP_SOLVE_TIMING (tuning aid): 1 = print every phase of the fast path to stderr as it ends; 2 = accumulate totals and
+// call counts per phase and print them once at exit (a print per call disturbs a 20 us phase and the ones after it).
+struct PhaseTotals {
+    static const int MAXP = 16;
+    std::mutex mu;
+    const char* name[MAXP];
+    double us[MAXP];
+    long calls[MAXP];
+    int n = 0;
+    void add(const char* what, double t) {
+        std::lock_guard<std::mutex> lk(mu);
+        int p = 0;
+        while (p < n && std::strcmp(name[p], what) != 0) ++p;
+        if (p == n) {
+            if (n == MAXP) return;
+            name[n] = what;
+            us[n] = 0.0;
+            calls[n] = 0;
+            ++n;
+        }
+        us[p] += t;
+        ++calls[p];
+    }
+    void print() {
+        std::lock_guard<std::mutex> lk(mu);
+        for (int p = 0; p < n; ++p)
+            std::fprintf(stderr, "[fsnap_solve] total %-26s %8ld calls %12.1f us  mean %9.2f us\n", name[p], calls[p], us[p],
+                         us[p] / (double)calls[p]);
+    }
+};
+PhaseTotals& phase_totals() {
+    static PhaseTotals* t = [] {
+        static PhaseTotals totals;
+        std::atexit([] { phase_totals().print(); });
+        return &totals;
+    }();
+    return *t;
+}
+struct PhaseTimer {
+    int mode;
     std::chrono::steady_clock::time_point t0;
-    PhaseTimer() : on(std::getenv("FSNAP_SOLVE_TIMING") != nullptr), t0(std::chrono::steady_clock::now()) {}
+    static int env_mode() {
+        static const int m = [] {
+            const char* e = std::getenv("FSNAP_SOLVE_TIMING");
+            if (!e) return 0;
+            return std::atoi(e) == 2 ? 2 : 1;
+        }();
+        return m;
+    }
+    PhaseTimer() : mode(env_mode()) {
+        if (mode) t0 = std::chrono::steady_clock::now();
+    }
     void lap(const char* what) {
-        if (!on) return;
+        if (!mode) return;
         const auto t1 = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[fsnap_solve] %-14s %9.1f us\n", what, std::chrono::duration<double, std::micro>(t1 - t0).count());
-        t0 = t1;
+        const double us = std::chrono::duration<double, std::micro>(t1 - t0).count();
+        if (mode == 2) phase_totals().add(what, us);
+        else std::fprintf(stderr, "[fsnap_solve] %-14s %9.1f us\n", what, us);
+        t0 = mode == 2 ? std::chrono::steady_clock::now() : t1;
     }
 };
 }  // namespace
@@ -837,77 +1148,70 @@ int solve_impl(int kind, double param, int64_t K64, const double* G, const doubl
             }
         }
         held.owner = nullptr;                 // the workspace is about to be overwritten
+        // small systems on one thread: scaling, factorisation and forward sweep as one left-looking pass over G
+        // (fused_scale_chol); its first two panels of G are fetched while the scaling vector is computed
+        const bool fused = use_fused_finish(Kp);
+        if (fused) prefetch_g_rows(G, K, 0, 16);
+        static thread_local vec uinv;
         U.resize((size_t)Kp * Kp);
         dsc.resize(Kp);
         z.resize(Kp);
         bool ok = true;
         double chk = 0.0;
-        for (int i = 0; i < K && ok; ++i) {
-            const double g = (diag ? diag[i] : G[(size_t)i * K + i]) + alpha;
-            if (!(g > 0.0) || !std::isfinite(g)) ok = false;
-            else dsc[i] = 1.0 / std::sqrt(g);
-            chk += c[i] * 0.0;
+        if (fused) {
+            uinv.resize(Kp);
+            if (!diag)
+                for (int i = 0; i < K; ++i) dsc[i] = G[(size_t)i * K + i];
+            ok = jacobi_scale(diag ? diag : dsc.data(), K, alpha, dsc.data());
+            bool fin = true;
+            for (int i = 0; i < K; ++i) {
+                z[i] = c[i] * dsc[i];
+                fin = fin && (c[i] - c[i] == 0.0);
+            }
+            for (int i = K; i < Kp; ++i) z[i] = 0.0;
+            if (!fin) chk = std::numeric_limits<double>::quiet_NaN();
+        } else {
+            for (int i = 0; i < K && ok; ++i) {
+                const double g = (diag ? diag[i] : G[(size_t)i * K + i]) + alpha;
+                if (!(g > 0.0) || !std::isfinite(g)) ok = false;
+                else dsc[i] = 1.0 / std::sqrt(g);
+                chk += c[i] * 0.0;
+            }
         }
         timer.lap("diag scale");
         if (ok) {
-            // rows are built in 8-wide vectors from the vector that holds the diagonal: the < 8 entries left of the
-            // diagonal receive (valid, unused) scaled values, everything further left is zeroed -- the blocked
-            // factorisation updates whole 32-column chunks.  The finiteness of everything read is folded into chkv.
-            const v8d zero = {0, 0, 0, 0, 0, 0, 0, 0};
-            v8d chk0 = zero, chk1 = zero;
-            for (int i = 0; i < K; ++i) {
-                const double* gi = G + (size_t)i * K;
-                double* ui = U.data() + (size_t)i * Kp;
-                const double di = dsc[i];
-                const v8d dv = {di, di, di, di, di, di, di, di};
-                const int j0 = i & ~7;
-                if (i + 2 < K) {     // the statistics were just written by the device: fetch the row after next early
-                    const double* gn = G + (size_t)(i + 2) * K;
-                    for (int jp = (i + 2) & ~7; jp < K; jp += 8) __builtin_prefetch(gn + jp, 0, 0);
-                }
-                int j = 0;
-                for (; j + 8 <= j0; j += 8) *(v8du*)(ui + j) = zero;
-                if (upper_only && j + 8 <= K) {
-                    // the vector that holds the diagonal: what lies left of it was never written by the device
-                    typedef long long v8l __attribute__((vector_size(64)));
-                    const v8l lanes = {0, 1, 2, 3, 4, 5, 6, 7};
-                    const v8l keep = (lanes + (long long)j) >= (long long)i;
-                    const v8d g0 = (v8d)((v8l)(*(const v8du*)(gi + j)) & keep);
-                    chk0 += g0 * zero;
-                    *(v8du*)(ui + j) = g0 * dv * *(const v8du*)(dsc.data() + j);
-                    j += 8;
-                }
-                for (; j + 16 <= K; j += 16) {
-                    const v8d g0 = *(const v8du*)(gi + j), g1 = *(const v8du*)(gi + j + 8);
-                    chk0 += g0 * zero;
-                    chk1 += g1 * zero;
-                    *(v8du*)(ui + j) = g0 * dv * *(const v8du*)(dsc.data() + j);
-                    *(v8du*)(ui + j + 8) = g1 * dv * *(const v8du*)(dsc.data() + j + 8);
-                }
-                for (; j + 8 <= K; j += 8) {
-                    const v8d g0 = *(const v8du*)(gi + j);
-                    chk0 += g0 * zero;
-                    *(v8du*)(ui + j) = g0 * dv * *(const v8du*)(dsc.data() + j);
-                }
-                for (; j < K; ++j) {
-                    const double gij = (upper_only && j < i) ? 0.0 : gi[j];
-                    ui[j] = gij * di * dsc[j];
-                    chk += gij * 0.0;
-                }
-                for (; j < Kp; ++j) ui[j] = 0.0;
-                ui[i] = (gi[i] + alpha) * di * di;
-            }
-            for (int i = K; i < Kp; ++i) {          // identity block of the padding
-                double* ui = U.data() + (size_t)i * Kp;
-                for (int j = 0; j < Kp; ++j) ui[j] = 0.0;
-                ui[i] = 1.0;
-            }
-            const v8d cs = chk0 + chk1;
-            chk += ((cs[0] + cs[1]) + (cs[2] + cs[3])) + ((cs[4] + cs[5]) + (cs[6] + cs[7]));
             double mp2 = 0.0;
-            timer.lap("scale/build");
-            const bool fact_ok = (chk == 0.0) && fast_chol(U.data(), Kp, &mp2) < 0;
-            timer.lap("cholesky");
+            bool fact_ok;
+            if (fused) {
+                double gchk = 0.0;
+                fact_ok = (chk == 0.0) &&
+                          fused_scale_chol(G, dsc.data(), K, Kp, alpha, upper_only, U.data(), z.data(), uinv.data(), &mp2, &gchk) < 0 &&
+                          gchk == 0.0;
+                timer.lap("fused finish");           // z holds U^-T (c * dsc) now: only the backward sweep is left
+            } else {
+                // rows are built in 8-wide vectors from the vector that holds the diagonal: the < 8 entries left of the
+                // diagonal receive (valid, unused) scaled values, everything further left is zeroed -- the blocked
+                // factorisation updates whole 32-column chunks.  The finiteness of everything read is folded into chkv.
+                const v8d zero = {0, 0, 0, 0, 0, 0, 0, 0};
+                v8d chk0 = zero, chk1 = zero;
+                for (int i = 0; i < K; ++i) {
+                    if (i + 2 < K) {     // the statistics were just written by the device: fetch the row after next early
+                        const double* gn = G + (size_t)(i + 2) * K;
+                        for (int jp = (i + 2) & ~7; jp < K; jp += 8) __builtin_prefetch(gn + jp, 0, 0);
+                    }
+                    scaled_row(G, dsc.data(), K, Kp, i, alpha, upper_only, U.data(), chk0, chk1, chk);
+                }
+                for (int i = K; i < Kp; ++i) {          // identity block of the padding
+                    double* ui = U.data() + (size_t)i * Kp;
+                    for (int j = 0; j < Kp; ++j) ui[j] = 0.0;
+                    ui[i] = 1.0;
+                }
+                const v8d cs = chk0 + chk1;
+                chk += ((cs[0] + cs[1]) + (cs[2] + cs[3])) + ((cs[4] + cs[5]) + (cs[6] + cs[7]));
+                timer.lap("scale/build");
+                fact_ok = (chk == 0.0) && fast_chol(U.data(), Kp, &mp2) < 0;
+                timer.lap("cholesky");
+            }
             // LSTSQ stands in for an SVD of the rows (svd.py:54), which knows the conditioning: the smallest pivot does not
             // (it bounds lambda_min from above only), so the factor is asked -- a few S^-1 applications, fsnap_condest.h.
             // A factor whose lambda_min is at the rounding level of the statistics is no solution: the general path decides.
@@ -926,11 +1230,15 @@ int solve_impl(int kind, double param, int64_t K64, const double* G, const doubl
                 const double piv = mp2;
                 if (ce.steps && ce.lambda_min < mp2) mp2 = ce.lambda_min;
                 fsnap_cond_note(piv, ce.lambda_min, ce.steps, 0);
-                for (int i = 0; i < K; ++i) z[i] = c[i] * dsc[i];
-                for (int i = K; i < Kp; ++i) z[i] = 0.0;
-                chol_solve(U.data(), Kp, z.data());
+                if (fused) {
+                    chol_back_inv(U.data(), Kp, z.data(), uinv.data());
+                } else {
+                    for (int i = 0; i < K; ++i) z[i] = c[i] * dsc[i];
+                    for (int i = K; i < Kp; ++i) z[i] = 0.0;
+                    chol_solve(U.data(), Kp, z.data());
+                }
                 for (int i = 0; i < K; ++i) beta[i] = z[i] * dsc[i];
-                timer.lap("tri solves");
+                timer.lap(fused ? "back sweep" : "tri solves");
                 if (all_finite(beta, K)) {
                     if (rank_out) *rank_out = K;
                     if (rcond_est) *rcond_est = mp2;
