@@ -26,7 +26,9 @@
 #include <utility>
 
 #include "fsnap_device_common.h"
+#include "fsnap_dispatch.h"
 #include "fsnap_kernels.h"
+#include "fsnap_wave_sum.h"
 
 namespace {
 
@@ -57,11 +59,6 @@ __device__ __forceinline__ void cat_for_impl(F&& f, std::integer_sequence<int, I
 template <int N, class F>
 __device__ __forceinline__ void cat_for(F&& f) {
     cat_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // offset of G[i][j] (i <= j) inside one chunk's tile partials [pair][reg][lane]: D row = (lane >> 4) + 4 reg, col = lane & 15
@@ -128,16 +125,14 @@ __device__ __forceinline__ void cat_syrk_wave(const double* __restrict__ A, int6
 #pragma unroll
         for (int g = 0; g < 4; ++g) pc[k * 256 + g * 64 + lane] = acc[J][g];
         if constexpr (p == q) {
-            double v = cacc[J];
-            v += __shfl_xor(v, 16, 64);
-            v += __shfl_xor(v, 32, 64);
+            const double v = ks_sum(cacc[J]);
             if (ks == 0) cpart[chunk * NT * 16 + 16 * p + e] = v;
         }
     });
     if constexpr (W == 0) {
-        s_bb = wave_sum(s_bb);
-        s_b = wave_sum(s_b);
-        s_n = wave_sum(s_n);
+        s_bb = wave_sum_desc(s_bb);
+        s_b = wave_sum_desc(s_b);
+        s_n = wave_sum_desc(s_n);
         if (lane == 0) {
             spart[chunk * 3 + 0] = s_bb;
             spart[chunk * 3 + 1] = s_b;
@@ -202,14 +197,13 @@ __global__ __launch_bounds__(256) void fsnap_cat_syrk_gen_k(const double* __rest
 #pragma unroll
     for (int g = 0; g < 4; ++g) pc[g * 64 + lane] = acc[g];
     if (p == q) {
-        cacc += __shfl_xor(cacc, 16, 64);
-        cacc += __shfl_xor(cacc, 32, 64);
+        cacc = ks_sum(cacc);
         if (ks == 0) cpart[chunk * NT * 16 + cp] = cacc;
     }
     if (k == 0) {
-        s_bb = wave_sum(s_bb);
-        s_b = wave_sum(s_b);
-        s_n = wave_sum(s_n);
+        s_bb = wave_sum_desc(s_bb);
+        s_b = wave_sum_desc(s_b);
+        s_n = wave_sum_desc(s_n);
         if (lane == 0) {
             spart[chunk * 3 + 0] = s_bb;
             spart[chunk * 3 + 1] = s_b;
@@ -361,8 +355,7 @@ __global__ __launch_bounds__(256) void fsnap_cand_rows_k(const double* __restric
         double v[4] = {s0, s1, s2, s3};
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            v[q] += __shfl_xor(v[q], 16, 64);
-            v[q] += __shfl_xor(v[q], 32, 64);
+            v[q] = ks_sum(v[q]);
             if (ks == 0) partial[(slot * 4 + q) * 16 + e] = v[q];
         }
     } else {
@@ -425,25 +418,16 @@ hipError_t launch_cat_syrk(const double* A, int64_t lda, const double* b, const 
     if (nchunks <= 0) return hipSuccess;
     const int NT = (K + 15) / 16;
     const dim3 grid((unsigned)nchunks);
-#define FSNAP_CAT_CASE(N) \
-    case N: fsnap_cat_syrk_k<N><<<grid, 256, 0, st>>>(A, lda, b, w0, idx, chunks, K, part, cpart, spart); break;
-    switch (NT) {
-        FSNAP_CAT_CASE(1)
-        FSNAP_CAT_CASE(2)
-        FSNAP_CAT_CASE(3)
-        FSNAP_CAT_CASE(4)
-        FSNAP_CAT_CASE(5)
-        FSNAP_CAT_CASE(6)
-        FSNAP_CAT_CASE(7)
-        FSNAP_CAT_CASE(8)
-        FSNAP_CAT_CASE(9)
-        default: {
+    dispatch_nt(NT, [&](auto nt) {
+        constexpr int N = decltype(nt)::value;
+        if constexpr (N > 0) {
+            fsnap_cat_syrk_k<N><<<grid, 256, 0, st>>>(A, lda, b, w0, idx, chunks, K, part, cpart, spart);
+        } else {
             const int NP = NT * (NT + 1) / 2;
             fsnap_cat_syrk_gen_k<<<dim3((unsigned)((NP + 3) / 4), (unsigned)nchunks), 256, 0, st>>>(A, lda, b, w0, idx, chunks, K, NT,
                                                                                                   part, cpart, spart);
         }
-    }
-#undef FSNAP_CAT_CASE
+    });
     return hipGetLastError();
 }
 

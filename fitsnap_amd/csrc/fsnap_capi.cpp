@@ -2640,6 +2640,69 @@ int fsnap_select_end(fsnap_ctx* ctx) {
     return FSNAP_OK;
 }
 
+namespace {
+
+// The sorted row index of a unit layout (configurations, units): offsets[0 ... count] (the caller's name for them: what) start
+// at 0 and do not decrease, there are at most m positions, and every position names a distinct row of the context -- a row
+// written by two units would be a race.  per_row_check(p, row) runs on every position that passed; a non-zero return ends the
+// check with that code.  rows_what / rows_given: the per-row arrays that must be there as soon as there is a position.
+template <class PerRow>
+int check_unit_index(fsnap_ctx* ctx, const char* who, const char* what, const int32_t* sorted_rows, const int64_t* offsets,
+                     int64_t count, int64_t m, PerRow&& per_row_check, const char* rows_what = "sorted_rows",
+                     bool rows_given = true) {
+    if (offsets[0] != 0) return ctx->fail(FSNAP_E_ARG, "%s: %s[0] = %lld", who, what, (long long)offsets[0]);
+    for (int64_t u = 0; u < count; ++u)
+        if (offsets[u + 1] < offsets[u]) return ctx->fail(FSNAP_E_ARG, "%s: %s decrease at %lld", who, what, (long long)u);
+    const int64_t npos = offsets[count];
+    if (npos > m) return ctx->fail(FSNAP_E_ARG, "%s: %lld positions for %lld rows", who, (long long)npos, (long long)m);
+    if (npos > 0 && (!sorted_rows || !rows_given)) return ctx->fail(FSNAP_E_ARG, "%s: %s is NULL", who, rows_what);
+    std::vector<unsigned char> seen((size_t)std::max<int64_t>(m, 1), 0);
+    for (int64_t p = 0; p < npos; ++p) {
+        const int32_t r = sorted_rows[p];
+        if (r < 0 || r >= m || seen[(size_t)r])
+            return ctx->fail(FSNAP_E_ARG, "%s: sorted_rows[%lld] = %d is out of range or repeated", who, (long long)p, r);
+        seen[(size_t)r] = 1;
+        if (const int rc = per_row_check(p, r)) return rc;
+    }
+    return FSNAP_OK;
+}
+
+// Units by solve size d = min(n, J): the LDS kernels take d <= 32 / 64 / lds_max (bins 0 ... 2), global scratch the rest
+// (bin 3, any d <= dmax).
+struct UnitBins {
+    int D[4];                          // the kernel class of each bin (0: global scratch)
+    std::vector<int32_t> lists[4];     // the units of each bin, in unit order
+    int nblk[4];                       // workgroups of each bin's launch
+    int64_t dmax = 0;                  // the largest d of bin 3 (0 when it is empty)
+};
+
+// size(u): the rows of unit u = 0 ... count - 1, 0 leaves the unit out.  all: the four lists one after the other.  Bins 0 ... 2
+// get at most 16 workgroups per CU; scratch(dmax) is the doubles of global scratch one workgroup of bin 3 needs: at most two
+// workgroups per CU and ~1 GiB of scratch in all.
+template <class Size, class Scratch>
+UnitBins bin_units(int64_t count, Size&& size, int64_t J, int lds_max, int num_cu, Scratch&& scratch, std::vector<int32_t>& all) {
+    UnitBins bins{{32, 64, lds_max, 0}, {}, {}, 0};
+    for (int64_t u = 0; u < count; ++u) {
+        const int64_t n = size(u);
+        if (n == 0) continue;
+        const int64_t d = std::min(n, J);
+        const int b = d <= 32 ? 0 : d <= 64 ? 1 : d <= lds_max ? 2 : 3;
+        bins.lists[b].push_back((int32_t)u);
+        if (b == 3) bins.dmax = std::max(bins.dmax, d);
+    }
+    all.clear();
+    for (auto& l : bins.lists) all.insert(all.end(), l.begin(), l.end());
+    const int nblk_lds = std::max(1, 16 * num_cu);
+    for (int b = 0; b < 3; ++b) bins.nblk[b] = (int)std::min<int64_t>((int64_t)bins.lists[b].size(), nblk_lds);
+    bins.nblk[3] = bins.lists[3].empty()
+                       ? 0
+                       : (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)bins.lists[3].size(), 2 * (int64_t)num_cu,
+                                                                      (int64_t)(1 << 27) / std::max<int64_t>(scratch(bins.dmax), 1)}));
+    return bins;
+}
+
+}  // namespace
+
 // ---- leave-one-configuration-out predictions of the resident training rows (kernels L1, L2 of fsnap_loco.hip) --------
 
 int fsnap_loco_rows(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, const double* beta, const int32_t* sorted_rows,
@@ -2655,22 +2718,9 @@ int fsnap_loco_rows(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, const
     if (m > 0 && K != ctx->K)
         return ctx->fail(FSNAP_E_ARG, "%s: K = %lld, the resident rows have %lld columns", who, (long long)K, (long long)ctx->K);
     if (m > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: needs m < 2^31", who);
-    if (cfg_offsets[0] != 0) return ctx->fail(FSNAP_E_ARG, "%s: cfg_offsets[0] = %lld", who, (long long)cfg_offsets[0]);
-    for (int64_t c = 0; c < ncfg; ++c)
-        if (cfg_offsets[c + 1] < cfg_offsets[c])
-            return ctx->fail(FSNAP_E_ARG, "%s: cfg_offsets decrease at %lld", who, (long long)c);
+    int rc = check_unit_index(ctx, who, "cfg_offsets", sorted_rows, cfg_offsets, ncfg, m, [](int64_t, int32_t) { return 0; });
+    if (rc) return rc;
     const int64_t npos = cfg_offsets[ncfg];
-    if (npos > m) return ctx->fail(FSNAP_E_ARG, "%s: %lld positions for %lld rows", who, (long long)npos, (long long)m);
-    if (npos > 0 && !sorted_rows) return ctx->fail(FSNAP_E_ARG, "%s: sorted_rows is NULL", who);
-    {   // every position names a distinct row of the context: a row written by two configurations would be a race
-        std::vector<unsigned char> seen((size_t)std::max<int64_t>(m, 1), 0);
-        for (int64_t p = 0; p < npos; ++p) {
-            const int32_t r = sorted_rows[p];
-            if (r < 0 || r >= m || seen[(size_t)r])
-                return ctx->fail(FSNAP_E_ARG, "%s: sorted_rows[%lld] = %d is out of range or repeated", who, (long long)p, r);
-            seen[(size_t)r] = 1;
-        }
-    }
     for (int64_t i = 0; i < m; ++i) pred_out[i] = std::numeric_limits<double>::quiet_NaN();
     for (int64_t c = 0; c < ncfg; ++c) {      // empty configurations: nothing to leave out
         cfg_info_out[4 * c] = 0.0;
@@ -2679,7 +2729,6 @@ int fsnap_loco_rows(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, const
         cfg_info_out[4 * c + 3] = 1.0;
     }
     if (npos == 0) return FSNAP_OK;
-    int rc;
     if ((rc = check_rows(ctx)) || (rc = check_weights(ctx))) return rc;
     FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
     if (ctx->uq_inflight) {
@@ -2689,33 +2738,17 @@ int fsnap_loco_rows(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, const
     int npk = 0;
     if ((rc = ensure_wpack(ctx, &npk))) return rc;
     const double* wpack = ctx->wpack_override ? ctx->wpack_override : (const double*)ctx->wpack.p;
-    // configurations by solve size d_c = min(n_c, J): LDS kernels for d <= 32 / 64 / 128, global scratch beyond
-    const int Dbin[4] = {32, 64, fsnap::LOCO_MAX_LDS_D, 0};
-    std::vector<int32_t> lists[4];
-    int64_t dmax = 0;
-    for (int64_t c = 0; c < ncfg; ++c) {
-        const int64_t n = cfg_offsets[c + 1] - cfg_offsets[c];
-        if (n == 0) continue;
-        const int64_t d = std::min(n, J);
-        const int b = d <= 32 ? 0 : d <= 64 ? 1 : d <= fsnap::LOCO_MAX_LDS_D ? 2 : 3;
-        lists[b].push_back((int32_t)c);
-        if (b == 3) dmax = std::max(dmax, d);
-    }
+    // configurations by solve size d_c = min(n_c, J); general path: one (dmax^2 + dmax) slice of scratch per workgroup
+    const UnitBins bins = bin_units(
+        ncfg, [&](int64_t c) { return cfg_offsets[c + 1] - cfg_offsets[c]; }, J, fsnap::LOCO_MAX_LDS_D, ctx->num_cu,
+        [](int64_t dmax) { return dmax * dmax + dmax; }, ctx->loco_hlist);
+    const int64_t dmax = bins.dmax, hslice = dmax * dmax + dmax;
+    const int* nblk = bins.nblk;
     const int64_t Kp = (K + 15) / 16 * 16, Jp = (J + 15) / 16 * 16;
     const size_t nM = (size_t)(Kp * Jp);
     ctx->loco_hM.assign(nM + (size_t)Kp, 0.0);
     for (int64_t k = 0; k < K; ++k) std::memcpy(&ctx->loco_hM[(size_t)(k * Jp)], M + k * J, (size_t)J * 8);
     std::memcpy(&ctx->loco_hM[nM], beta, (size_t)K * 8);
-    ctx->loco_hlist.clear();
-    for (auto& l : lists) ctx->loco_hlist.insert(ctx->loco_hlist.end(), l.begin(), l.end());
-    const int nblk_lds = std::max(1, 16 * ctx->num_cu);
-    int nblk[4];
-    for (int b = 0; b < 3; ++b) nblk[b] = (int)std::min<int64_t>((int64_t)lists[b].size(), nblk_lds);
-    // general path: one (dmax^2 + dmax) slice per workgroup, at most ~1 GiB of scratch and two workgroups per CU
-    const int64_t hslice = dmax * dmax + dmax;
-    nblk[3] = lists[3].empty() ? 0
-                               : (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)lists[3].size(), 2 * (int64_t)ctx->num_cu,
-                                                                              (int64_t)(1 << 27) / std::max<int64_t>(hslice, 1)}));
     const int nvg = std::max({nblk[0], nblk[1], nblk[2], nblk[3], 1});
     if (!ctx->loco_M.ensure((nM + (size_t)Kp) * 8) || !ctx->loco_idx.ensure((size_t)npos * 4) ||
         !ctx->loco_off.ensure((size_t)(ncfg + 1) * 8) || !ctx->loco_list.ensure(std::max<size_t>(ctx->loco_hlist.size(), 1) * 4) ||
@@ -2740,9 +2773,9 @@ int fsnap_loco_rows(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, const
               "launch fsnap_loco_zeta_k");
     size_t first = 0;
     for (int b = 0; b < 4; ++b) {
-        const int ncl = (int)lists[b].size();
+        const int ncl = (int)bins.lists[b].size();
         if (ncl > 0)
-            FSNAP_HIP(fsnap::launch_loco_cfg(Dbin[b], nblk[b], (const double*)ctx->loco_Z.p, (int)Jp, (int)J, aux, aux + npos,
+            FSNAP_HIP(fsnap::launch_loco_cfg(bins.D[b], nblk[b], (const double*)ctx->loco_Z.p, (int)Jp, (int)J, aux, aux + npos,
                                              aux + 2 * npos, (const int*)ctx->loco_idx.p, (const int64_t*)ctx->loco_off.p,
                                              (const int*)ctx->loco_list.p + first, ncl, (double*)ctx->loco_H.p, (int)dmax,
                                              (double*)ctx->loco_v.p, (double*)ctx->loco_pred.p, (double*)ctx->loco_info.p,
@@ -2781,24 +2814,18 @@ int fsnap_ridge_path(fsnap_ctx* ctx, int64_t K, const double* G, const double* c
     if (m > 0 && K != ctx->K)
         return ctx->fail(FSNAP_E_ARG, "%s: K = %lld, the resident rows have %lld columns", who, (long long)K, (long long)ctx->K);
     if (m > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: needs m < 2^31", who);
-    if (unit_offsets[0] != 0) return ctx->fail(FSNAP_E_ARG, "%s: unit_offsets[0] = %lld", who, (long long)unit_offsets[0]);
-    for (int64_t u = 0; u < nunits; ++u)
-        if (unit_offsets[u + 1] < unit_offsets[u])
-            return ctx->fail(FSNAP_E_ARG, "%s: unit_offsets decrease at %lld", who, (long long)u);
+    // the two trailing arguments keep this entry point's own message for a missing per-row array ("sorted_rows / row_class is
+    // NULL", raised where the other callers raise "sorted_rows is NULL"); the class of every listed row is checked as it passes
+    int rc = check_unit_index(
+        ctx, who, "unit_offsets", sorted_rows, unit_offsets, nunits, m,
+        [&](int64_t, int32_t r) {
+            return row_class[r] < nclass ? FSNAP_OK
+                                         : ctx->fail(FSNAP_E_ARG, "%s: row %d has class %d, nclass = %lld", who, r, (int)row_class[r],
+                                                     (long long)nclass);
+        },
+        "sorted_rows / row_class", row_class != nullptr);
+    if (rc) return rc;
     const int64_t npos = unit_offsets[nunits];
-    if (npos > m) return ctx->fail(FSNAP_E_ARG, "%s: %lld positions for %lld rows", who, (long long)npos, (long long)m);
-    if (npos > 0 && (!sorted_rows || !row_class)) return ctx->fail(FSNAP_E_ARG, "%s: sorted_rows / row_class is NULL", who);
-    {   // every position names a distinct row of the context and a class below nclass
-        std::vector<unsigned char> seen((size_t)std::max<int64_t>(m, 1), 0);
-        for (int64_t p = 0; p < npos; ++p) {
-            const int32_t r = sorted_rows[p];
-            if (r < 0 || r >= m || seen[(size_t)r])
-                return ctx->fail(FSNAP_E_ARG, "%s: sorted_rows[%lld] = %d is out of range or repeated", who, (long long)p, r);
-            seen[(size_t)r] = 1;
-            if (row_class[r] >= nclass)
-                return ctx->fail(FSNAP_E_ARG, "%s: row %d has class %d, nclass = %lld", who, r, (int)row_class[r], (long long)nclass);
-        }
-    }
     const size_t nsum = (size_t)Q * (size_t)nunits * (size_t)nclass * 4, ninfo = (size_t)Q * (size_t)nunits * 2;
     if (npos == 0) {                              // no rows at all: every unit is empty, nothing to leave out
         std::fill(sums_out, sums_out + nsum, 0.0);
@@ -2809,7 +2836,6 @@ int fsnap_ridge_path(fsnap_ctx* ctx, int64_t K, const double* G, const double* c
         if (pred_out) std::fill(pred_out, pred_out + (size_t)Q * (size_t)m, std::numeric_limits<double>::quiet_NaN());
         return FSNAP_OK;
     }
-    int rc;
     if ((rc = check_rows(ctx)) || (rc = check_weights(ctx))) return rc;
     FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
     if (ctx->uq_inflight) {
@@ -2871,23 +2897,11 @@ int fsnap_joint_begin(fsnap_ctx* ctx, const int32_t* sorted_rows, const int64_t*
     if (nunits < 0 || nunits > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: nunits = %lld", who, (long long)nunits);
     const int64_t m = ctx->m;
     if (m > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: needs m < 2^31", who);
-    if (unit_offsets[0] != 0) return ctx->fail(FSNAP_E_ARG, "%s: unit_offsets[0] = %lld", who, (long long)unit_offsets[0]);
-    for (int64_t u = 0; u < nunits; ++u)
-        if (unit_offsets[u + 1] < unit_offsets[u]) return ctx->fail(FSNAP_E_ARG, "%s: unit_offsets decrease at %lld", who, (long long)u);
+    if (const int rc = check_unit_index(ctx, who, "unit_offsets", sorted_rows, unit_offsets, nunits, m, [](int64_t, int32_t) { return 0; }))
+        return rc;
     const int64_t npos = unit_offsets[nunits];
-    if (npos > m) return ctx->fail(FSNAP_E_ARG, "%s: %lld positions for %lld rows", who, (long long)npos, (long long)m);
-    if (npos > 0 && !sorted_rows) return ctx->fail(FSNAP_E_ARG, "%s: sorted_rows is NULL", who);
     std::vector<double> hom((size_t)std::max<int64_t>(npos, 1), 1.0);
-    {   // every position names a distinct row of the context
-        std::vector<unsigned char> seen((size_t)std::max<int64_t>(m, 1), 0);
-        for (int64_t p = 0; p < npos; ++p) {
-            const int32_t r = sorted_rows[p];
-            if (r < 0 || r >= m || seen[(size_t)r])
-                return ctx->fail(FSNAP_E_ARG, "%s: sorted_rows[%lld] = %d is out of range or repeated", who, (long long)p, r);
-            seen[(size_t)r] = 1;
-            if (omega) hom[(size_t)p] = omega[r];
-        }
-    }
+    for (int64_t p = 0; omega && p < npos; ++p) hom[(size_t)p] = omega[sorted_rows[p]];
     if (npos > 0) {
         int rc = check_rows(ctx);
         if (rc) return rc;
@@ -2934,19 +2948,14 @@ int fsnap_joint_score(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, int
         if (gain) gain[u] = nan;
         if (reduction) reduction[u] = nan;
     }
-    // live units by dim S = min(n_u, J): LDS kernels for <= 32 / 64 / 128, global scratch beyond
-    const int Dbin[4] = {32, 64, fsnap::JOINT_MAX_LDS_D, 0};
-    std::vector<int32_t> lists[4];
-    int64_t dmax = 0;
-    for (int64_t u = 0; u < nunits; ++u) {
-        if (!ctx->joint_halive[(size_t)u]) continue;
-        const int64_t d = std::min(ctx->joint_hoff[(size_t)u + 1] - ctx->joint_hoff[(size_t)u], J);
-        const int b = d <= 32 ? 0 : d <= 64 ? 1 : d <= fsnap::JOINT_MAX_LDS_D ? 2 : 3;
-        lists[b].push_back((int32_t)u);
-        if (b == 3) dmax = std::max(dmax, d);
-    }
-    ctx->joint_hlist.clear();
-    for (auto& l : lists) ctx->joint_hlist.insert(ctx->joint_hlist.end(), l.begin(), l.end());
+    // live units by dim S = min(n_u, J); general path: S (dmax^2 + dmax) and the Y fragments per workgroup
+    const UnitBins bins = bin_units(
+        nunits,
+        [&](int64_t u) { return ctx->joint_halive[(size_t)u] ? ctx->joint_hoff[(size_t)u + 1] - ctx->joint_hoff[(size_t)u] : 0; }, J,
+        fsnap::JOINT_MAX_LDS_D, ctx->num_cu, [](int64_t dmax) { return dmax * dmax + dmax + fsnap::joint_yslice(dmax); },
+        ctx->joint_hlist);
+    const int64_t dmax = bins.dmax;
+    const int* nblk = bins.nblk;
     if (ctx->joint_hlist.empty() || npos == 0) return FSNAP_OK;
     if ((rc = check_rows(ctx))) return rc;
     FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
@@ -2964,13 +2973,7 @@ int fsnap_joint_score(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, int
     }
     ctx->joint_hB.assign((size_t)std::max<int64_t>(Jp * rp, 1), 0.0);
     for (int64_t j = 0; j < J && r > 0; ++j) std::memcpy(&ctx->joint_hB[(size_t)(j * rp)], B + j * r, (size_t)r * 8);
-    const int nblk_lds = std::max(1, 16 * ctx->num_cu);
-    int nblk[4];
-    for (int b = 0; b < 3; ++b) nblk[b] = (int)std::min<int64_t>((int64_t)lists[b].size(), nblk_lds);
     const int64_t sslice = dmax * dmax + dmax, yslice = fsnap::joint_yslice(dmax);
-    nblk[3] = lists[3].empty() ? 0
-                               : (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)lists[3].size(), 2 * (int64_t)ctx->num_cu,
-                                                                              (int64_t)(1 << 27) / std::max<int64_t>(sslice + yslice, 1)}));
     if (!ctx->joint_F.ensure((size_t)(Kp * Wp) * 8) || !ctx->joint_B.ensure(ctx->joint_hB.size() * 8) ||
         !ctx->joint_ZP.ensure((size_t)npos * (size_t)Wp * 8) || !ctx->joint_list.ensure(ctx->joint_hlist.size() * 4) ||
         !ctx->joint_out.ensure((size_t)nunits * 2 * 8) || !ctx->joint_info.ensure((size_t)nunits * 4 * 8) ||
@@ -2987,9 +2990,9 @@ int fsnap_joint_score(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, int
               "launch fsnap_joint_rows_k");
     size_t first = 0;
     for (int b = 0; b < 4; ++b) {
-        const int ncl = (int)lists[b].size();
+        const int ncl = (int)bins.lists[b].size();
         if (ncl > 0)
-            FSNAP_HIP(fsnap::launch_joint_units(Dbin[b], nblk[b], (const double*)ctx->joint_ZP.p, (int)Wp, (int)Jp, (int)J, (int)rp,
+            FSNAP_HIP(fsnap::launch_joint_units(bins.D[b], nblk[b], (const double*)ctx->joint_ZP.p, (int)Wp, (int)Jp, (int)J, (int)rp,
                                                 (const double*)ctx->joint_B.p, tau, (const int64_t*)ctx->joint_off.p,
                                                 (const int*)ctx->joint_list.p + first, ncl, (double*)ctx->joint_S.p, (int)dmax,
                                                 (double*)ctx->joint_Y.p, (double*)ctx->joint_out.p, (double*)ctx->joint_info.p,

@@ -27,7 +27,9 @@
 // Every sum runs in a fixed order that depends on the unit's own rows (and M, B, tau) only: a unit's scores are bit-identical
 // under repeats and under any permutation or subset of the units.  No atomics; results are written with vector stores.
 #include "fsnap_device_common.h"
+#include "fsnap_dispatch.h"
 #include "fsnap_kernels.h"
+#include "fsnap_wave_sum.h"
 
 namespace {
 
@@ -90,12 +92,6 @@ __global__ __launch_bounds__(256) void fsnap_joint_rows_k(const double* __restri
             for (int g = 0; g < 4; ++g) dst[4 * g] = wgt[r] * acc[r][g];
         }
     }
-}
-
-__device__ __forceinline__ double joint_wave_sum(double v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // Forward substitution L Y = RHS for the rp (a multiple of 16) columns of rhs (element (i, c) at rhs[i * ldr + c], rows
@@ -278,7 +274,7 @@ __device__ __forceinline__ void joint_one_unit(const double* __restrict__ ZP, in
         double sb, sy;
         const double* rhs = nspace ? Zu + Jp : Bp;
         joint_subst<NTD>(H, ldh, d, rhs, nspace ? Wp : rp, rp, yg + (int64_t)wave * (4 * ntmax * 64), sb, sy);
-        part = joint_wave_sum(nspace ? sy : sb - sy);
+        part = wave_sum(nspace ? sy : sb - sy);
     }
     if (lane == 0) ws[wave] = part;
     __syncthreads();
@@ -330,25 +326,9 @@ hipError_t launch_joint_rows(const double* A, int64_t lda, int K, const int* idx
     if (npos <= 0) return hipSuccess;
     const int64_t per_block = 4 * 16 * JOINT_RB;
     const dim3 grid((unsigned)((npos + per_block - 1) / per_block));
-    const int NT = (K + 15) / 16;
-#define FSNAP_JOINT_CASE(N)                                                                   \
-    case N:                                                                                   \
-        fsnap_joint_rows_k<N><<<grid, 256, 0, st>>>(A, lda, K, idx, npos, om, Fp, Wp, ZP);    \
-        break;
-    switch (NT) {
-        FSNAP_JOINT_CASE(1)
-        FSNAP_JOINT_CASE(2)
-        FSNAP_JOINT_CASE(3)
-        FSNAP_JOINT_CASE(4)
-        FSNAP_JOINT_CASE(5)
-        FSNAP_JOINT_CASE(6)
-        FSNAP_JOINT_CASE(7)
-        FSNAP_JOINT_CASE(8)
-        FSNAP_JOINT_CASE(9)
-        default:
-            fsnap_joint_rows_k<0><<<grid, 256, 0, st>>>(A, lda, K, idx, npos, om, Fp, Wp, ZP);
-    }
-#undef FSNAP_JOINT_CASE
+    dispatch_nt((K + 15) / 16, [&](auto nt) {
+        fsnap_joint_rows_k<decltype(nt)::value><<<grid, 256, 0, st>>>(A, lda, K, idx, npos, om, Fp, Wp, ZP);
+    });
     return hipGetLastError();
 }
 
@@ -357,13 +337,10 @@ hipError_t launch_joint_units(int D, int nblocks, const double* ZP, int Wp, int 
                               double* info, hipStream_t st) {
     if (ncl <= 0 || nblocks <= 0) return hipSuccess;
     const dim3 grid((unsigned)nblocks);
-    switch (D) {
-        case 32: fsnap_joint_unit_k<32><<<grid, 256, 0, st>>>(ZP, Wp, Jp, J, rp, Bp, tau, off, ulist, ncl, Sg, dmax, Yg, out, info); break;
-        case 64: fsnap_joint_unit_k<64><<<grid, 256, 0, st>>>(ZP, Wp, Jp, J, rp, Bp, tau, off, ulist, ncl, Sg, dmax, Yg, out, info); break;
-        case 128: fsnap_joint_unit_k<128><<<grid, 256, 0, st>>>(ZP, Wp, Jp, J, rp, Bp, tau, off, ulist, ncl, Sg, dmax, Yg, out, info); break;
-        case 0: fsnap_joint_unit_k<0><<<grid, 256, 0, st>>>(ZP, Wp, Jp, J, rp, Bp, tau, off, ulist, ncl, Sg, dmax, Yg, out, info); break;
-        default: return hipErrorInvalidValue;
-    }
+    const bool known = dispatch_d(D, [&](auto dd) {
+        fsnap_joint_unit_k<decltype(dd)::value><<<grid, 256, 0, st>>>(ZP, Wp, Jp, J, rp, Bp, tau, off, ulist, ncl, Sg, dmax, Yg, out, info);
+    });
+    if (!known) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -23,17 +23,13 @@
 // configuration's own rows only (zeta_i on a_i and M alone, as in fsnap_uq.hip), so a row's result is bit-identical under
 // repeats and under any permutation of the configurations.  No atomics; results are written with vector stores.
 #include "fsnap_device_common.h"
+#include "fsnap_dispatch.h"
 #include "fsnap_kernels.h"
+#include "fsnap_wave_sum.h"
 
 namespace {
 
 constexpr int LOCO_RB = 2;   // 16-position blocks per wave in kernel L1
-
-__device__ __forceinline__ double loco_ks_sum(double v) {
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
 
 template <int NT>
 __global__ __launch_bounds__(256) void fsnap_loco_zeta_k(const double* __restrict__ A, int64_t lda, int K,
@@ -74,7 +70,7 @@ __global__ __launch_bounds__(256) void fsnap_loco_zeta_k(const double* __restric
         } else {
             for (int s = 0; s < ns; ++s) p = __builtin_fma(ld(r, 4 * s + ks), bp[4 * s + ks], p);
         }
-        p = loco_ks_sum(p);
+        p = ks_sum(p);
         if (ks == 0 && valid[r]) {
             const double w = wpack[2 * row[r]], wb = wpack[2 * row[r] + 1];
             pb[pos[r]] = p;
@@ -297,25 +293,9 @@ hipError_t launch_loco_zeta(const double* A, int64_t lda, int K, const int* idx,
     if (npos <= 0) return hipSuccess;
     const int64_t per_block = 4 * 16 * LOCO_RB;
     const dim3 grid((unsigned)((npos + per_block - 1) / per_block));
-    const int NT = (K + 15) / 16;
-#define FSNAP_LOCO_CASE(N)                                                                                          \
-    case N:                                                                                                         \
-        fsnap_loco_zeta_k<N><<<grid, 256, 0, st>>>(A, lda, K, idx, npos, wpack, Mp, Jp, bp, Z, pw, pe, pb);         \
-        break;
-    switch (NT) {
-        FSNAP_LOCO_CASE(1)
-        FSNAP_LOCO_CASE(2)
-        FSNAP_LOCO_CASE(3)
-        FSNAP_LOCO_CASE(4)
-        FSNAP_LOCO_CASE(5)
-        FSNAP_LOCO_CASE(6)
-        FSNAP_LOCO_CASE(7)
-        FSNAP_LOCO_CASE(8)
-        FSNAP_LOCO_CASE(9)
-        default:
-            fsnap_loco_zeta_k<0><<<grid, 256, 0, st>>>(A, lda, K, idx, npos, wpack, Mp, Jp, bp, Z, pw, pe, pb);
-    }
-#undef FSNAP_LOCO_CASE
+    dispatch_nt((K + 15) / 16, [&](auto nt) {
+        fsnap_loco_zeta_k<decltype(nt)::value><<<grid, 256, 0, st>>>(A, lda, K, idx, npos, wpack, Mp, Jp, bp, Z, pw, pe, pb);
+    });
     return hipGetLastError();
 }
 
@@ -324,13 +304,10 @@ hipError_t launch_loco_cfg(int D, int nblocks, const double* Z, int Jp, int J, c
                            int dmax, double* vg, double* pred, double* info, hipStream_t st) {
     if (ncl <= 0 || nblocks <= 0) return hipSuccess;
     const dim3 grid((unsigned)nblocks);
-    switch (D) {
-        case 32: fsnap_loco_cfg_k<32><<<grid, 256, 0, st>>>(Z, Jp, J, pw, pe, pb, idx, off, clist, ncl, Hg, dmax, vg, pred, info); break;
-        case 64: fsnap_loco_cfg_k<64><<<grid, 256, 0, st>>>(Z, Jp, J, pw, pe, pb, idx, off, clist, ncl, Hg, dmax, vg, pred, info); break;
-        case 128: fsnap_loco_cfg_k<128><<<grid, 256, 0, st>>>(Z, Jp, J, pw, pe, pb, idx, off, clist, ncl, Hg, dmax, vg, pred, info); break;
-        case 0: fsnap_loco_cfg_k<0><<<grid, 256, 0, st>>>(Z, Jp, J, pw, pe, pb, idx, off, clist, ncl, Hg, dmax, vg, pred, info); break;
-        default: return hipErrorInvalidValue;
-    }
+    const bool known = dispatch_d(D, [&](auto dd) {
+        fsnap_loco_cfg_k<decltype(dd)::value><<<grid, 256, 0, st>>>(Z, Jp, J, pw, pe, pb, idx, off, clist, ncl, Hg, dmax, vg, pred, info);
+    });
+    if (!known) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

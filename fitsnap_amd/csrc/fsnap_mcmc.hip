@@ -20,6 +20,7 @@
 // of a ragged last block) are dropped by selects: NaN / Inf in them reach nothing.  No atomics; results are written with
 // vector stores.
 #include "fsnap_device_common.h"
+#include "fsnap_dispatch.h"
 #include "fsnap_kernels.h"
 
 namespace {
@@ -129,25 +130,10 @@ void sse_pack_u(const double* U, int P, int K, double* Up) {
 hipError_t launch_sse_batch(const double* A, int64_t lda, int64_t m, int K, const double* Up, const double* b, const double* w,
                             const unsigned char* mask, double* partial, double* out, hipStream_t st) {
     const int nb = sse_num_blocks(m);
-    const int nt = (K + 15) / 16;
-#define FSNAP_SSE_CASE(N)                                                                                                  \
-    case N:                                                                                                                \
-        hipLaunchKernelGGL((fsnap_sse_rows_k<N>), dim3((unsigned)nb), dim3(256), 0, st, A, lda, m, K, Up, b, w, mask, partial); \
-        break;
-    switch (nt) {
-        FSNAP_SSE_CASE(1)
-        FSNAP_SSE_CASE(2)
-        FSNAP_SSE_CASE(3)
-        FSNAP_SSE_CASE(4)
-        FSNAP_SSE_CASE(5)
-        FSNAP_SSE_CASE(6)
-        FSNAP_SSE_CASE(7)
-        FSNAP_SSE_CASE(8)
-        FSNAP_SSE_CASE(9)
-        default:
-            hipLaunchKernelGGL((fsnap_sse_rows_k<0>), dim3((unsigned)nb), dim3(256), 0, st, A, lda, m, K, Up, b, w, mask, partial);
-    }
-#undef FSNAP_SSE_CASE
+    dispatch_nt((K + 15) / 16, [&](auto nt) {
+        hipLaunchKernelGGL((fsnap_sse_rows_k<decltype(nt)::value>), dim3((unsigned)nb), dim3(256), 0, st, A, lda, m, K, Up, b, w, mask,
+                           partial);
+    });
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return launch_colsum(partial, nb, SSE_NCOL, out, st);

@@ -4,6 +4,7 @@
 #pragma once
 #include "fsnap_device_common.h"
 #include "fsnap_kernels.h"
+#include "fsnap_wave_sum.h"
 
 namespace fsnap_rowvar {
 
@@ -13,13 +14,6 @@ template <int MODE>
 __device__ __forceinline__ double fold(double v, double t, double a) {
     if constexpr (MODE == fsnap::UQ_QUAD) return __builtin_fma(t, a, v);
     else return __builtin_fma(t, t, v);
-}
-
-// sum over the four lanes e, e + 16, e + 32, e + 48 (fixed order)
-__device__ __forceinline__ double ks_sum(double v) {
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
 }
 
 // Any K (untuned): a wave takes RB blocks of 16 rows; the row values are loaded per k step of every M tile.

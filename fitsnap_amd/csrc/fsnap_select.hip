@@ -18,14 +18,13 @@
 // a_i, its old variance and V alone -- bit-identical run to run and under any row subset, permutation, m or lda.  Category
 // sums follow the stable-sorted row order.  No atomics; every result is written with vector stores.
 #include "fsnap_device_common.h"
+#include "fsnap_dispatch.h"
 #include "fsnap_kernels.h"
 #include "fsnap_rowvar_body.h"
 
 namespace {
 
 constexpr int SEL_RB = fsnap_rowvar::RB;   // 16-row blocks per wave
-
-__device__ __forceinline__ double sel_ks_sum(double v) { return fsnap_rowvar::ks_sum(v); }
 
 // fragments of V in flight: a divisor of NS (the slot of fragment s is s % PF in every tile), 7 ... 12 where there is one
 constexpr int sel_prefetch_depth(int ns) {
@@ -87,7 +86,7 @@ __global__ __launch_bounds__(256, 2) void fsnap_sel_rows_k(const double* __restr
     }
 #pragma unroll
     for (int r = 0; r < SEL_RB; ++r) {
-        const double s = sel_ks_sum(v[r]);
+        const double s = ks_sum(v[r]);
         if (ks == 0 && valid[r]) var[row[r]] = var[row[r]] - s;
     }
 }
@@ -168,25 +167,11 @@ hipError_t launch_sel_rows(const double* A, int64_t lda, int64_t m, int K, const
     if (m <= 0) return hipSuccess;
     const int64_t rows_per_block = 4 * 16 * SEL_RB;
     const dim3 grid((unsigned)((m + rows_per_block - 1) / rows_per_block));
-    const int NT = (K + 15) / 16;
-#define FSNAP_SEL_CASE(N)                                                     \
-    case N:                                                                   \
-        fsnap_sel_rows_k<N><<<grid, 256, 0, st>>>(A, lda, m, K, Vp, Jp, var); \
-        break;
-    switch (NT) {
-        FSNAP_SEL_CASE(1)
-        FSNAP_SEL_CASE(2)
-        FSNAP_SEL_CASE(3)
-        FSNAP_SEL_CASE(4)
-        FSNAP_SEL_CASE(5)
-        FSNAP_SEL_CASE(6)
-        FSNAP_SEL_CASE(7)
-        FSNAP_SEL_CASE(8)
-        FSNAP_SEL_CASE(9)
-        default:
-            fsnap_sel_rows_gen_k<<<grid, 256, 0, st>>>(A, lda, m, K, Vp, Jp, var);
-    }
-#undef FSNAP_SEL_CASE
+    dispatch_nt((K + 15) / 16, [&](auto nt) {
+        constexpr int N = decltype(nt)::value;
+        if constexpr (N > 0) fsnap_sel_rows_k<N><<<grid, 256, 0, st>>>(A, lda, m, K, Vp, Jp, var);
+        else fsnap_sel_rows_gen_k<<<grid, 256, 0, st>>>(A, lda, m, K, Vp, Jp, var);
+    });
     return hipGetLastError();
 }
 

@@ -21,19 +21,13 @@
 // are bit-identical under any row subset, permutation, m or lda.  Category sums follow the stable-sorted row order.  No
 // atomics; every result is written with vector stores.
 #include "fsnap_device_common.h"
+#include "fsnap_dispatch.h"
 #include "fsnap_kernels.h"
 #include "fsnap_rowvar_body.h"
 
 namespace {
 
 constexpr int UQ_RB = fsnap_rowvar::RB;   // 16-row blocks per wave
-
-template <int MODE>
-__device__ __forceinline__ double uq_fold(double v, double t, double a) {
-    return fsnap_rowvar::fold<MODE>(v, t, a);
-}
-
-__device__ __forceinline__ double uq_ks_sum(double v) { return fsnap_rowvar::ks_sum(v); }
 
 template <int NT, int MODE>
 __global__ __launch_bounds__(256, 2) void fsnap_uq_rows_k(const double* __restrict__ A, int64_t lda, int64_t m, int K,
@@ -65,7 +59,7 @@ __global__ __launch_bounds__(256, 2) void fsnap_uq_rows_k(const double* __restri
             double p = 0.0;
 #pragma unroll
             for (int s = 0; s < NS; ++s) p = __builtin_fma(x[r][s], bp[4 * s + ks], p);
-            p = uq_ks_sum(p);
+            p = ks_sum(p);
             if (ks == 0 && valid[r]) preds[row[r]] = p;
         }
     }
@@ -99,12 +93,12 @@ __global__ __launch_bounds__(256, 2) void fsnap_uq_rows_k(const double* __restri
                     const int k = 16 * jt + ks + 4 * g;
                     if (valid[r] && k < K) a = src[r][k];
                 }
-                v[r] = uq_fold<MODE>(v[r], acc[r][g], a);     // NORM: padding columns of M are zero, they add nothing
+                v[r] = fsnap_rowvar::fold<MODE>(v[r], acc[r][g], a);     // NORM: padding columns of M are zero, they add nothing
             }
     }
 #pragma unroll
     for (int r = 0; r < UQ_RB; ++r) {
-        const double s = uq_ks_sum(v[r]);
+        const double s = ks_sum(v[r]);
         if (ks == 0 && valid[r]) var[row[r]] = s;
     }
 }
@@ -143,27 +137,15 @@ hipError_t launch_uq_rows(int mode, const double* A, int64_t lda, int64_t m, int
     if (m <= 0) return hipSuccess;
     const int64_t rows_per_block = 4 * 16 * UQ_RB;
     const dim3 grid((unsigned)((m + rows_per_block - 1) / rows_per_block));
-    const int NT = (K + 15) / 16;
-#define FSNAP_UQ_CASE(N)                                                                                   \
-    case N:                                                                                                \
-        if (mode == UQ_QUAD) fsnap_uq_rows_k<N, UQ_QUAD><<<grid, 256, 0, st>>>(A, lda, m, K, Mp, Jp, bp, var, preds); \
-        else fsnap_uq_rows_k<N, UQ_NORM><<<grid, 256, 0, st>>>(A, lda, m, K, Mp, Jp, bp, var, preds);              \
-        break;
-    switch (NT) {
-        FSNAP_UQ_CASE(1)
-        FSNAP_UQ_CASE(2)
-        FSNAP_UQ_CASE(3)
-        FSNAP_UQ_CASE(4)
-        FSNAP_UQ_CASE(5)
-        FSNAP_UQ_CASE(6)
-        FSNAP_UQ_CASE(7)
-        FSNAP_UQ_CASE(8)
-        FSNAP_UQ_CASE(9)
-        default:
-            if (mode == UQ_QUAD) fsnap_uq_rows_gen_k<UQ_QUAD><<<grid, 256, 0, st>>>(A, lda, m, K, Mp, Jp, bp, var, preds);
-            else fsnap_uq_rows_gen_k<UQ_NORM><<<grid, 256, 0, st>>>(A, lda, m, K, Mp, Jp, bp, var, preds);
-    }
-#undef FSNAP_UQ_CASE
+    auto launch = [&](auto nt, auto md) {
+        constexpr int N = decltype(nt)::value, MODE = decltype(md)::value;
+        if constexpr (N > 0) fsnap_uq_rows_k<N, MODE><<<grid, 256, 0, st>>>(A, lda, m, K, Mp, Jp, bp, var, preds);
+        else fsnap_uq_rows_gen_k<MODE><<<grid, 256, 0, st>>>(A, lda, m, K, Mp, Jp, bp, var, preds);
+    };
+    dispatch_nt((K + 15) / 16, [&](auto nt) {
+        if (mode == UQ_QUAD) launch(nt, std::integral_constant<int, UQ_QUAD>{});
+        else launch(nt, std::integral_constant<int, UQ_NORM>{});
+    });
     return hipGetLastError();
 }
 

@@ -31,7 +31,7 @@ def main():
             rows[cur][m.group(1).strip()] = int(m.group(2))
     for name, r in rows.items():
         dem = subprocess.run(["c++filt", name], stdout=subprocess.PIPE, text=True).stdout.strip()
-        dem = re.sub(r"\(.*", "", dem)
+        dem = re.sub(r"\(.*", "", dem.replace("(anonymous namespace)::", ""))
         if flt and flt not in dem:
             continue
         print(f"{dem:60s} VGPR {r.get('VGPRs', -1):4d} AGPR {r.get('AGPRs', -1):4d} SGPR {r.get('SGPRs', -1):4d} "
