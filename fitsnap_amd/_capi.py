@@ -125,6 +125,8 @@ SIGNATURES = {
                                 c_void_p]),
     "fsnap_ridge_path": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
                                  c_int64, c_void_p, c_void_p, c_void_p]),
+    "fsnap_lasso_path": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_double, c_void_p,
+                                 c_void_p, c_void_p]),
     "fsnap_select_begin": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int]),
     "fsnap_select_pick": (c_int, [c_void_p, c_int, POINTER(ctypes.c_int32), POINTER(c_double)]),
     "fsnap_select_retire": (c_int, [c_void_p, ctypes.c_int32]),
@@ -1010,6 +1012,20 @@ class HipContext:
                                                _ptr(off), nunits, _ptr(cls) if cls.size else None, nclass, _ptr(sums),
                                                _ptr(info), _ptr(preds) if want_preds else None))
         return sums, info, preds
+
+    def lasso_path(self, d_stats_ptr: int, K: int, F: int, nsub: int, alphas, max_iter: int, tol: float):
+        """Grouped K-fold LASSO alpha path on per-fold statistics in device memory (``fsnap_lasso_path``, K <= 144):
+        ``d_stats_ptr`` is the device address of F * nsub packed blocks (``cat_normal_eq``), fold f the sum of ``nsub``
+        consecutive ones.  Returns (coef ((F + 1) x Q x K; index F: no fold left out), info ((F + 1) x Q x 4: sweeps, last
+        duality gap, l1_reg, n), heldout (F x Q x 3: n_f, weighted squared error of fold f under its own refit, bb_f))."""
+        alphas = _f64(alphas, "alphas").reshape(-1)
+        K, F, Q = int(K), int(F), alphas.size
+        coef = np.empty((max(F, 0) + 1, Q, max(K, 0)))
+        info = np.empty((max(F, 0) + 1, Q, 4))
+        held = np.empty((max(F, 0), Q, 3))
+        self._check(self._lib.fsnap_lasso_path(self._h, K, F, int(nsub), c_void_p(d_stats_ptr), _ptr(alphas) if Q else None, Q,
+                                               int(max_iter), float(tol), _ptr(coef), _ptr(info), _ptr(held)))
+        return coef, info, held
 
     def lstsq_rows(self, rcond: float, K: int = None):
         """``lstsq(aw, bw, rcond)`` of the resident rows computed on the rows (fsnap_lstsq_rows); collective when the

@@ -2877,6 +2877,53 @@ int fsnap_ridge_path(fsnap_ctx* ctx, int64_t K, const double* G, const double* c
     return FSNAP_OK;
 }
 
+// ---- grouped K-fold LASSO alpha paths on the per-fold statistics (kernels S1, S2 of fsnap_lasso.hip) -------------------
+
+int fsnap_lasso_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const double* d_stats, const double* alphas, int64_t Q,
+                     int64_t max_iter, double tol, double* coef_out, double* info_out, double* heldout_out) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_lasso_path";
+    if (!d_stats || !alphas || !coef_out || !info_out || !heldout_out) return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
+    if (K < 1 || K > fsnap::LASSO_MAX_K)
+        return ctx->fail(FSNAP_E_ARG, "%s: K = %lld (1 ... %d)", who, (long long)K, fsnap::LASSO_MAX_K);
+    if (F < 1 || nsub < 1 || F > 0x3FFFFFFF || nsub > 0x3FFFFFFF)
+        return ctx->fail(FSNAP_E_ARG, "%s: F = %lld, nsub = %lld", who, (long long)F, (long long)nsub);
+    if (Q < 1 || Q > 0xFFFFF || (F + 1) * Q > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: Q = %lld", who, (long long)Q);
+    if (max_iter < 1 || max_iter > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: max_iter = %lld", who, (long long)max_iter);
+    if (!std::isfinite(tol) || tol < 0.0) return ctx->fail(FSNAP_E_ARG, "%s: tol = %g is negative or not finite", who, tol);
+    for (int64_t q = 0; q < Q; ++q)
+        if (!std::isfinite(alphas[q]) || alphas[q] < 0.0)
+            return ctx->fail(FSNAP_E_ARG, "%s: alphas[%lld] = %g is negative or not finite", who, (long long)q, alphas[q]);
+    if (!cand_fits(F * nsub, K))
+        return ctx->fail(FSNAP_E_ARG, "%s: %lld blocks x %lld doubles exceed FSNAP_CAT_STATS_MAX_BYTES", who, (long long)(F * nsub),
+                         (long long)FSNAP_PACKED_LEN(K));
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    const int64_t T = FSNAP_PACKED_LEN(K), nprob = (F + 1) * Q;
+    const int64_t nfold = nsub > 1 ? F : 0;                 // nsub = 1: the caller's blocks are the folds
+    if (!ctx->lasso_sys.ensure((size_t)(nfold + 1) * T * 8) || !ctx->lasso_alphas.ensure((size_t)Q * 8) ||
+        !ctx->lasso_coef.ensure((size_t)nprob * K * 8) || !ctx->lasso_info.ensure((size_t)nprob * 4 * 8) ||
+        !ctx->lasso_held.ensure((size_t)F * Q * 3 * 8))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(lasso path) failed");
+    double* dfolds = nfold ? (double*)ctx->lasso_sys.p : nullptr;
+    double* dtotal = (double*)ctx->lasso_sys.p + nfold * T;
+    FSNAP_HIP(hipMemcpyAsync(ctx->lasso_alphas.p, alphas, (size_t)Q * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(alphas)");
+    FSNAP_HIP(fsnap::launch_lasso_folds(d_stats, (int)F, (int)nsub, (int)K, dfolds, dtotal, ctx->stream),
+              "launch fsnap_lasso_folds_k");
+    const int nblocks = (int)std::min<int64_t>(nprob, (int64_t)fsnap::lasso_blocks_per_cu((int)K) * std::max(1, ctx->num_cu));
+    FSNAP_HIP(fsnap::launch_lasso_cd(nblocks, dfolds ? dfolds : d_stats, dtotal, (const double*)ctx->lasso_alphas.p, (int)K, (int)F,
+                                     (int)Q, (int)max_iter, tol, (double*)ctx->lasso_coef.p, (double*)ctx->lasso_info.p,
+                                     (double*)ctx->lasso_held.p, ctx->stream),
+              "launch fsnap_lasso_cd_k");
+    FSNAP_HIP(hipMemcpyAsync(coef_out, ctx->lasso_coef.p, (size_t)nprob * K * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(coef)");
+    FSNAP_HIP(hipMemcpyAsync(info_out, ctx->lasso_info.p, (size_t)nprob * 4 * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(info)");
+    FSNAP_HIP(hipMemcpyAsync(heldout_out, ctx->lasso_held.p, (size_t)F * Q * 3 * 8, hipMemcpyDeviceToHost, ctx->stream),
+              "hipMemcpy(heldout)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    for (int64_t i = 0; i < nprob * K; ++i)
+        if (!std::isfinite(coef_out[i])) return FSNAP_NUM_NONFINITE;
+    return FSNAP_OK;
+}
+
 // ---- joint information-gain / variance-reduction scores of units (kernels J1, J2 of fsnap_joint.hip) ------------------
 
 namespace {

@@ -143,6 +143,8 @@ struct fsnap_ctx {
     // fsnap_ridge_path: [G | c | alphas], row classes, per-workgroup base tiles, sums, info, predictions (the unit index and
     // offsets share loco_idx / loco_off); kept between calls
     DevBuf path_in, path_cls, path_base, path_sums, path_info, path_pred;
+    // fsnap_lasso_path: [fold blocks (nsub > 1 only) | total], alphas, coefficients, info, held-out sums; kept between calls
+    DevBuf lasso_sys, lasso_alphas, lasso_coef, lasso_info, lasso_held;
     // fsnap_joint_*: the session's unit-sorted row index, unit offsets and per-position weights (uploaded once by begin), the
     // padded factor [M | M B] and B, Z / Pi per position (npos x Wp), the bucketed list of live units, per-unit (gain, reduction)
     // and info, per-workgroup scratch (S and the right-hand-side fragments of units too large for LDS); the host keeps the

@@ -253,6 +253,20 @@ hipError_t launch_ridge_path(int nblocks, const double* A, int64_t lda, int K, c
                              const double* alphas, int Q, const unsigned char* rcls, int nclass, double* Bg, double* sums,
                              double* info, double* pred, int64_t m, hipStream_t st);
 
+// Grouped K-fold LASSO alpha paths (fsnap_lasso.hip; K <= LASSO_MAX_K).  Kernel S1: folds[f] (F packed blocks of K^2 + K + 3
+// doubles; nullptr with nsub = 1, where the blocks of stats are the folds) = the sum of blocks f nsub ... f nsub + nsub - 1 of
+// stats, total = the sum of the folds, both in index order.
+constexpr int LASSO_MAX_K = 144;
+hipError_t launch_lasso_folds(const double* stats, int F, int nsub, int K, double* folds, double* total, hipStream_t st);
+// Kernel S2: problem p = f Q + q (f = F: no fold left out) is fsnap_lasso_gram on (total - folds[f]) with l1_reg = alphas[q] n,
+// from zeros; a coordinate j with total G_jj = 0 or downdated G_jj <= LOCO_PIVOT_TOL total G_jj is skipped.  coef[p][K],
+// info[p][4] = (sweeps, last duality gap, l1_reg, n), heldout[p][3] (p < F Q) = (n_f, bb_f - 2 beta . c_f + beta^T G_f beta, bb_f).
+// One wave per workgroup, nblocks workgroups stride over the problems.  All pointers: device.
+size_t lasso_lds_bytes(int K);
+int lasso_blocks_per_cu(int K);
+hipError_t launch_lasso_cd(int nblocks, const double* folds, const double* total, const double* alphas, int K, int F, int Q,
+                           int max_iter, double tol, double* coef, double* info, double* heldout, hipStream_t st);
+
 // Joint unit scores (fsnap_joint.hip).  Kernel J1: for the npos positions of the unit-sorted row index idx,
 // ZP[p] = om[p] a_idx[p] [M | M B] (Wp doubles per position; Fp: device, Kp x Wp row-major, zero-padded: columns [0, Jp) the
 // factor M, columns [Jp, Wp) the target block M B; Wp = Jp without a target; om: the weight of every position).

@@ -229,6 +229,49 @@ def choose_method(method, K):
     return method
 
 
+def resolve_rows(solver, who, by, fs_dict=None, b=None, w=None):
+    """Labels, truths and weights of the rows of the last fit, as ``loco_errors`` resolves them: ``fs_dict=None`` takes
+    ``pt.fitsnap_dict`` (``pt.local_lists`` on several ranks) and the shared ``b`` / ``w``; an explicit ``fs_dict`` needs
+    ``b`` and ``w`` (one weight per row, per training row, or one for all).  Returns (labels, b, w, testing mask, sorted
+    Row_Type names -- the union over the ranks --, class id per row, number of classes)."""
+    pt = solver.pt
+    if fs_dict is None:
+        labels = pt.local_lists if (pt.multi and getattr(pt, "local_lists", None)) else pt.fitsnap_dict
+        b = pt.shared_arrays["b"].array
+        w = pt.shared_arrays["w"].array
+    elif b is None or w is None:
+        raise ValueError(f"{who}: with fs_dict, pass the truths b and weights w of the fit too")
+    else:
+        labels = fs_dict
+    b = np.asarray(b, dtype=np.float64).reshape(-1)
+    m = b.shape[0]
+    if by not in labels:
+        raise KeyError(f"{who}: no '{by}' labels")
+    testing = np.asarray(labels["Testing"], dtype=bool) if "Testing" in labels else np.zeros(m, dtype=bool)
+    train = ~testing
+    w = np.asarray(w, dtype=np.float64).reshape(-1)
+    if w.size == 1:
+        w = np.full(m, float(w[0]))
+    elif w.size == int(train.sum()) and w.size != m:
+        wf = np.zeros(m)
+        wf[train] = w
+        w = wf
+    if w.size != m:
+        raise ValueError(f"{who}: {w.size} weights for {m} rows")
+    if len(labels[by]) != m:
+        raise ValueError(f"{who}: {len(labels[by])} '{by}' labels for {m} rows: not the rows of the resident fit")
+    rtypes = list(labels["Row_Type"]) if "Row_Type" in labels else ["Row"] * m
+    names = sorted(set(rtypes))
+    if pt.multi:
+        names = sorted({n for part in pt.allgather_object(names) for n in part})
+    if len(names) > MAX_CLASS:
+        raise ValueError(f"{who}: {len(names)} row types, at most {MAX_CLASS}")
+    pos = {n: i for i, n in enumerate(names)}
+    row_class = np.fromiter((pos[t] for t in rtypes), dtype=np.uint8, count=m)
+    nclass = max(len(names), 1)
+    return labels, b, w, testing, names, row_class, nclass
+
+
 def ridge_path(solver, alphas, by="Configs", fs_dict=None, b=None, w=None, method="auto", want_preds=False):
     """``Solver.ridge_path``: see there."""
     from pandas import DataFrame
@@ -248,40 +291,8 @@ def ridge_path(solver, alphas, by="Configs", fs_dict=None, b=None, w=None, metho
     c = np.ascontiguousarray(stats[1], dtype=np.float64).reshape(-1)
     K = G.shape[0]
     method = choose_method(method, K)
-    if fs_dict is None:
-        labels = pt.local_lists if (pt.multi and getattr(pt, "local_lists", None)) else pt.fitsnap_dict
-        b = pt.shared_arrays["b"].array
-        w = pt.shared_arrays["w"].array
-    elif b is None or w is None:
-        raise ValueError("ridge_path: with fs_dict, pass the truths b and weights w of the fit too")
-    else:
-        labels = fs_dict
-    b = np.asarray(b, dtype=np.float64).reshape(-1)
-    m = b.shape[0]
-    if by not in labels:
-        raise KeyError(f"ridge_path: no '{by}' labels")
-    testing = np.asarray(labels["Testing"], dtype=bool) if "Testing" in labels else np.zeros(m, dtype=bool)
-    train = ~testing
-    w = np.asarray(w, dtype=np.float64).reshape(-1)
-    if w.size == 1:
-        w = np.full(m, float(w[0]))
-    elif w.size == int(train.sum()) and w.size != m:
-        wf = np.zeros(m)
-        wf[train] = w
-        w = wf
-    if w.size != m:
-        raise ValueError(f"ridge_path: {w.size} weights for {m} rows")
-    if len(labels[by]) != m:
-        raise ValueError(f"ridge_path: {len(labels[by])} '{by}' labels for {m} rows: not the rows of the resident fit")
-    rtypes = list(labels["Row_Type"]) if "Row_Type" in labels else ["Row"] * m
-    names = sorted(set(rtypes))
-    if pt.multi:
-        names = sorted({n for part in pt.allgather_object(names) for n in part})
-    if len(names) > MAX_CLASS:
-        raise ValueError(f"ridge_path: {len(names)} row types, at most {MAX_CLASS}")
-    pos = {n: i for i, n in enumerate(names)}
-    row_class = np.fromiter((pos[t] for t in rtypes), dtype=np.uint8, count=m)
-    nclass = max(len(names), 1)
+    labels, b, w, testing, names, row_class, nclass = resolve_rows(solver, who, by, fs_dict, b, w)
+    m, train = b.shape[0], ~testing
     sorted_rows, offsets, units = loco.unit_index(labels[by], train)
     if pt.multi:
         try:

@@ -25,7 +25,7 @@ import numpy as np
 
 from .. import _capi
 from .._hostblas import blas_threads
-from . import loco, ridge_path, select, select_joint, uq
+from . import lasso_path, loco, ridge_path, select, select_joint, uq
 
 
 class _TrainWeights:
@@ -1166,3 +1166,31 @@ class Solver:
         config is changed: write ``best_alpha`` into ``[RIDGE] alpha`` and fit.  Raises ValueError for other solvers, for
         ``apply_transpose``, for an SVD fit that took the row-space path and for rows that are not those of the fit."""
         return ridge_path.ridge_path(self, alphas, by, fs_dict, b, w, method, want_preds)
+
+    # ------------------------------------------------------------------------------
+    # grouped K-fold LASSO alpha paths (solvers/lasso_path.py, csrc/fsnap_lasso.hip)
+    # ------------------------------------------------------------------------------
+    def lasso_path(self, alphas, folds=5, by="Configs", fs_dict=None, b=None, w=None, tol=None, max_iter=None, method="auto",
+                   table="auto", seed=0):
+        """Grouped K-fold cross-validation of the LASSO fit over a grid of alphas (scikit-learn's ``LassoCV`` with a
+        ``GroupKFold``), after ``perform_fit`` of a LASSO solver, from ONE pass over the resident training rows: the units
+        (``fs_dict[by]``, as in ``loco_errors``) are dealt into folds, the statistics of every fold are formed on the GPU and
+        every (fold left out, alpha) refit plus the fit on all rows per alpha runs as coordinate descent on "total minus
+        fold".  ``folds``: an int F (units in sorted key order, shuffled by ``numpy.random.default_rng(seed)``, dealt
+        round-robin), ``None`` (every unit its own fold) or a mapping from unit to fold.  ``tol`` defaults to ``LASSO.TOL``,
+        ``max_iter`` to the ``[LASSO]`` section's.  ``method``: "device" (the kernel, K <= 144), "host"
+        (``fsnap_lasso_gram`` over the downloaded fold statistics) or "auto" (the kernel where it exists).  ``table``:
+        "rows" (one pass over the rows with the F x Q held-out coefficient vectors: ncount / mae / rmse / w_rmse of the
+        held-out rows per (alpha, Row_Type), pooled over the folds, laid out as ``ridge_path``'s table), "stats" (the
+        weighted error alone, from the statistics; what stays affordable with thousands of folds) or "auto" (rows while
+        F Q <= 512).  Labels, truths and weights as in ``loco_errors``; the statistics and the row pass read the RESIDENT
+        rows, truths and weights of the fit, so an explicit ``b`` / ``w`` is checked for its length only.  Both tables come
+        from one layout, fold x row class (the folds alone, and the statistics table only, where that many blocks would pass
+        ``FSNAP_CAT_STATS_MAX_BYTES``).  Collective on several ranks; a unit may span ranks.
+        Returns ``LassoPath(alphas, fits, nonzeros, sweeps, gaps, converged, table, fold_of_unit, cv_error, cv_se, best,
+        best_alpha, sparsest, sparsest_alpha)``: the Q x K fits on all training rows and their non-zero counts; sweeps, last
+        duality gaps and convergence flags ((F + 1) x Q, row F the fits on all rows); ``cv_error`` the pooled weighted
+        held-out mean squared error per alpha and ``cv_se`` its standard error over the folds; ``best`` the grid index of
+        the minimum (ties to the larger alpha) and ``sparsest`` that of the largest alpha within one ``cv_se`` of it.
+        Neither the fit nor the config is changed.  Raises ValueError for other solvers and for ``apply_transpose``."""
+        return lasso_path.lasso_path(self, alphas, folds, by, fs_dict, b, w, tol, max_iter, method, table, seed)

@@ -384,6 +384,25 @@ int fsnap_ridge_path(fsnap_ctx* ctx, int64_t K, const double* G, const double* c
                      const int32_t* sorted_rows, const int64_t* unit_offsets, int64_t nunits, const uint8_t* row_class,
                      int64_t nclass, double* sums_out, double* info_out, double* pred_out);
 
+/* Grouped K-fold LASSO alpha paths on per-fold statistics (kernels S1, S2 of csrc/fsnap_lasso.hip; what LassoCV with a
+ * GroupKFold is to Lasso; the folds, routes and tables are solvers/lasso_path.py).  d_stats (DEVICE) holds F * nsub packed
+ * blocks of FSNAP_PACKED_LEN(K) doubles as fsnap_cat_normal_eq / fsnap_cat_normal_eq_dist leave them; fold f is the sum of the
+ * blocks f * nsub ... f * nsub + nsub - 1 and the total T the sum of the folds, both added in index order.  Problem (f, q),
+ * f < F: the refit without fold f; f = F: the fit on all training rows:
+ *     Qm = T.G - G_f,  qv = T.c - c_f,  y2 = T.bb - bb_f,  n = T.n - n_f,  l1_reg = alphas[q] * n       (f = F: T alone)
+ * solved as fsnap_lasso_gram solves it, statement for statement, from zeros (every problem starts cold; the sums of the duality
+ * gap alone run in another order).  Coordinate j is dead -- skipped, coefficient 0, q_j taken as 0 -- when T.G_jj == 0 or
+ * Qm_jj <= 1e-10 T.G_jj (the fold alone touched the column and the subtraction left noise); a problem without a live
+ * coordinate (an empty training set) ends after its first sweep.  Outputs (host):
+ * coef_out[(F + 1)][Q][K]; info_out[(F + 1)][Q][4] = sweeps run, the last duality gap, l1_reg, n; heldout_out[F][Q][3] = n_f,
+ * bb_f - 2 beta . c_f + beta^T G_f beta (the weighted squared error of fold f under its own refit), bb_f.  FSNAP_E_ARG for K
+ * outside 1 ... 144, F < 1, nsub < 1, Q < 1, max_iter < 1, a negative or non-finite alpha or tol, a NULL pointer, or F * nsub
+ * blocks past FSNAP_CAT_STATS_MAX_BYTES.  No atomics; a problem's result depends on its own (fold, alpha) only: bit-identical
+ * run to run and under any permutation or subset of the grid.  The resident rows, weights, mask and category layout are not
+ * touched.  Synchronous. */
+int fsnap_lasso_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const double* d_stats, const double* alphas, int64_t Q,
+                     int64_t max_iter, double tol, double* coef_out, double* info_out, double* heldout_out);
+
 /* Joint scores of units (normally configurations) of the resident rows for active learning (kernels J1, J2 of
  * csrc/fsnap_joint.hip, fp64 MFMA; the host algebra is solvers/select_joint.py).  With the posterior C = M M^T (M: K x J),
  * the noise variance tau of a unit-weight row, the weighted rows X_u = diag(omega) A_u (n_u x K) of unit u, Z = X_u M and a
