@@ -230,6 +230,7 @@ __global__ __launch_bounds__(256) void fsnap_assemble_k(const double* __restrict
 // keeps the GPU path within 1e-6 of the reference's lstsq (svd.py:54) on ill-conditioned A.
 // Workgroup = row range, cut into 4 * 64 / L interleaved row streams; a lane owns two adjacent columns per pass.
 // Per-workgroup partial vectors are written to spart2[wg][K] and summed in fixed order.
+// Rows with u_i == 0 take no part (selects): the test rows of a refinement step may hold NaN / Inf, as in the SYRK.
 // ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void fsnap_gemvT_rows_k(const double* __restrict__ A, int64_t lda,
                                                           const double* __restrict__ u, int64_t m, int K,
@@ -259,7 +260,14 @@ __global__ __launch_bounds__(256) void fsnap_gemvT_rows_k(const double* __restri
                 const double u0 = u[row], u1 = u[row + NS];
                 const d2u x = *reinterpret_cast<const d2u*>(A + row * lda + c);
                 const d2u y = *reinterpret_cast<const d2u*>(A + (row + NS) * lda + c);
-                const double x0 = x[0], x1 = two ? x[1] : 0.0, y0 = y[0], y1 = two ? y[1] : 0.0;
+                // a row with u = 0 (a test row: kernel 4 writes an exact zero there) contributes nothing, whatever it holds:
+                // NaN / Inf in it are selected away, as in kernel 4+7.  On finite rows fma(x, 0, acc) and fma(0, 0, acc)
+                // are both acc, except for the sign of a zero: an accumulator is -0.0 only after nothing but products that
+                // underflowed to -0, and while it is, x < 0 keeps -0.0 where the select gives +0.0.  Any later non-zero
+                // product and the fold below (t starts at +0.0) erase that sign: partial[] has the bits of the plain products.
+                const bool z0 = u0 == 0.0, z1 = u1 == 0.0;
+                const double x0 = z0 ? 0.0 : x[0], x1 = (two && !z0) ? x[1] : 0.0;
+                const double y0 = z1 ? 0.0 : y[0], y1 = (two && !z1) ? y[1] : 0.0;
                 a0 = __builtin_fma(x0, u0, a0);
                 a1 = __builtin_fma(x1, u0, a1);
                 b0 = __builtin_fma(y0, u1, b0);
@@ -267,8 +275,10 @@ __global__ __launch_bounds__(256) void fsnap_gemvT_rows_k(const double* __restri
             }
             for (; row < r1; row += NS) {
                 const double u0 = u[row];
-                const double x0 = A[row * lda + c];
-                const double x1 = two ? A[row * lda + c + 1] : 0.0;
+                const bool z0 = u0 == 0.0;
+                const double l0 = A[row * lda + c];
+                const double l1 = two ? A[row * lda + c + 1] : 0.0;
+                const double x0 = z0 ? 0.0 : l0, x1 = z0 ? 0.0 : l1;
                 a0 = __builtin_fma(x0, u0, a0);
                 a1 = __builtin_fma(x1, u0, a1);
             }
@@ -469,7 +479,16 @@ __global__ __launch_bounds__(256) void fsnap_error_stats_k(const double* __restr
             atomicAdd(e + 3, w * t);
         } else {
             const double r = t - pred[row], wr = w * r;
-            const double dt = t - means[2 * c], dwt = w * t - means[2 * c + 1];
+            const double dt = t - means[2 * c];
+            // w t is rounded as in pass 0 and not fused into the subtraction (device code contracts by default): the
+            // weighted mean of a one-row category is that product, so its spread is the exact zero of the reference's
+            // float64 array expression
+            double dwt;
+            {
+#pragma clang fp contract(off)
+                const double wt = w * t;
+                dwt = wt - means[2 * c + 1];
+            }
             atomicAdd(e + 0, fabs(r));
             atomicAdd(e + 1, r * r);
             atomicAdd(e + 2, dt * dt);

@@ -1,17 +1,21 @@
-"""Per-call wall times of fsnap_residual_rhs (one pass / two passes) at a few shapes: looks for outliers."""
+"""Per-call wall times of fsnap_residual_rhs (one pass / two passes) at a few shapes: looks for outliers.
+``residual_probe.py M K [M K ...]`` times those shapes instead (K > 288 has the two-kernel form only)."""
 import sys, time
 import numpy as np
 sys.path.insert(0, ".")
 from fitsnap_amd import _capi
 from fitsnap_amd.synthetic import synth_problem
 
-for m, K in ((1_000_000, 31), (1_000_000, 64), (1_000_000, 128), (4_000_000, 31), (200_000, 200)):
+shapes = ((1_000_000, 31), (1_000_000, 64), (1_000_000, 128), (4_000_000, 31), (200_000, 200))
+if len(sys.argv) > 1:
+    shapes = tuple(zip(map(int, sys.argv[1::2]), map(int, sys.argv[2::2])))
+for m, K in shapes:
     A, b, w = synth_problem(m, K)
     ctx = _capi.HipContext(0)
     ctx.upload_rows(A, b)
     ctx.set_weights(w)
     beta = ctx.fit_resident(_capi.SOLVE_RIDGE, 1e-8)[0]
-    for mode in (1, 2, 0):
+    for mode in ((1, 0) if K <= 288 else (0,)):
         ctx.set_option("fused_residual", mode)
         ts = []
         for i in range(14):

@@ -1082,8 +1082,8 @@ def test_residual_rhs_general_k(ctx, K):
 def test_one_pass_residual_rhs(ctx, K, m):
     # fsnap_residual_rhs for K <= 288: kernels 4 + 7 fused, every row read once (option fused_residual: 1 = the default
     # form, 0 = the two-kernel form that wider systems take).  Both against the
-    # oracle's s = aw^T (bw - aw beta) and SSE on the training rows; NaN / Inf in A, b, w of test rows reach nothing in the
-    # fused forms (the reference drops those rows by fancy indexing, svd.py:44-46).
+    # oracle's s = aw^T (bw - aw beta) and SSE on the training rows; NaN / Inf in A, b, w of test rows reach nothing in
+    # either form (the reference drops those rows by fancy indexing, svd.py:44-46).
     rng = np.random.default_rng(6000 + K)
     A, b, w = orc.synth_problem(m, K)
     t = rng.random(m) < 0.2
@@ -1099,9 +1099,8 @@ def test_one_pass_residual_rhs(ctx, K, m):
     try:
         for mode in (1, 0):
             ctx.set_option("fused_residual", mode)
-            dirty = mode != 0                      # the two-kernel form multiplies masked rows by u = 0: finite rows only
-            ctx.upload_rows(A2 if dirty else A, b2 if dirty else b)
-            ctx.set_weights(w2 if dirty else w, (~t).astype(np.uint8))
+            ctx.upload_rows(A2, b2)                # both forms: kernel 7 skips the rows whose u is zero
+            ctx.set_weights(w2, (~t).astype(np.uint8))
             s, sse = ctx.residual_rhs(beta, want_sse=True)
             assert np.isfinite(s).all()
             assert np.max(np.abs(s - ref) / scale) < 1e-13
