@@ -1046,20 +1046,46 @@ extern "C" __attribute__((visibility("hidden"))) double fsnap_gen_eig_max(const 
     forward_columns(C);
     for (int i = 0; i < k; ++i)
         for (int j = i + 1; j < k; ++j) C[(size_t)i * k + j] = C[(size_t)j * k + i] = 0.5 * (C[(size_t)i * k + j] + C[(size_t)j * k + i]);
-    // largest eigenvalue of the k x k matrix C: Lanczos with full re-orthogonalisation (a dozen matrix-vector products of k^2
-    // flops; the cyclic Jacobi sweeps this replaced took 0.25 ms at k = 31 -- more than the launch they follow)
-    const double* Cp = C.data();
-    vec tmp((size_t)k);
-    const fsnap::CondEstimate top = fsnap::lanczos_lambda_min(k, [Cp, k, &tmp](double* x) {
-        for (int i = 0; i < k; ++i) {
-            double acc = 0.0;
-            for (int j = 0; j < k; ++j) acc += Cp[(size_t)i * k + j] * x[j];
-            tmp[i] = acc;
+    // largest eigenvalue of the k x k matrix C, to rounding: Householder reduction to tridiagonal form (4/3 k^3 flops: 40 000 at
+    // k = 31) and bisection on the Sturm count.  (Until the device chain was pinned to a long-double reference this was a Lanczos
+    // run that stopped once a step raised the Ritz value by less than 25 %: theta came out 0.5 ... 9 % short of the eigenvalue, the
+    // estimate that much too large; the cyclic Jacobi sweeps before that took 0.25 ms.)
+    vec ta((size_t)k), tb((size_t)k), hv((size_t)k), hp((size_t)k);
+    for (int j = 0; j + 2 < k; ++j) {
+        const int m = k - j - 1;                               // order of the trailing block the reflector acts on
+        double nrm2 = 0.0;
+        for (int i = 0; i < m; ++i) {
+            hv[i] = C[(size_t)(j + 1 + i) * k + j];
+            nrm2 += hv[i] * hv[i];
         }
-        for (int i = 0; i < k; ++i) x[i] = tmp[i];
-        return true;
-    }, 4, 16);
-    return top.lambda_min > 0.0 && std::isfinite(top.lambda_min) ? 1.0 / top.lambda_min : -1.0;
+        const double nrm = std::sqrt(nrm2);
+        ta[j] = C[(size_t)j * k + j];
+        tb[j] = nrm;
+        if (!(nrm > 0.0)) continue;                            // column already reduced
+        hv[0] += hv[0] >= 0.0 ? nrm : -nrm;
+        double vn = 0.0;
+        for (int i = 0; i < m; ++i) vn += hv[i] * hv[i];
+        vn = 1.0 / std::sqrt(vn);
+        for (int i = 0; i < m; ++i) hv[i] *= vn;
+        // A <- (I - 2 v v^T) A (I - 2 v v^T) = A - 2 v w^T - 2 w v^T with p = A v, w = p - (v . p) v
+        double vp = 0.0;
+        for (int r = 0; r < m; ++r) {
+            double acc = 0.0;
+            for (int c = 0; c < m; ++c) acc += C[(size_t)(j + 1 + r) * k + j + 1 + c] * hv[c];
+            hp[r] = acc;
+            vp += hv[r] * acc;
+        }
+        for (int r = 0; r < m; ++r) hp[r] -= vp * hv[r];
+        for (int r = 0; r < m; ++r)
+            for (int c = 0; c < m; ++c) C[(size_t)(j + 1 + r) * k + j + 1 + c] -= 2.0 * (hv[r] * hp[c] + hp[r] * hv[c]);
+    }
+    if (k >= 2) {
+        ta[k - 2] = C[(size_t)(k - 2) * k + k - 2];
+        tb[k - 2] = C[(size_t)(k - 1) * k + k - 2];
+    }
+    ta[k - 1] = C[(size_t)(k - 1) * k + k - 1];
+    const double theta = fsnap::tridiag_lambda_max(ta.data(), tb.data(), k);
+    return theta > 0.0 && std::isfinite(theta) ? theta : -1.0;
 }
 
 extern "C" int fsnap_solve(int kind, double param, int64_t K64, const double* G, const double* c, double* beta,

@@ -17,6 +17,7 @@ from fitsnap_amd.parallel_tools import ParallelTools
 from fitsnap_amd.solvers import solver_factory
 from oracle import fitsnap_oracle as orc
 
+from chol_cases import conditioned
 from conftest import maxrel
 
 pytestmark = pytest.mark.gpu
@@ -27,18 +28,6 @@ def make_svd():
     pt = ParallelTools()
     cfg = Config(pt, {"SOLVER": {"solver": "SVD"}})
     return pt, solver_factory.solver("SVD", pt, cfg)
-
-
-def conditioned(m, K, kappa, mode, seed):
-    r = np.random.default_rng(seed)
-    U, _ = np.linalg.qr(r.standard_normal((m, K)))
-    V, _ = np.linalg.qr(r.standard_normal((K, K)))
-    if mode == "geometric":
-        s = np.logspace(0, -np.log10(kappa), K)
-    else:
-        s = np.ones(K)
-        s[-1] = 1.0 / kappa
-    return (U * s) @ V.T
 
 
 def extended_precision_solution(A, b, start):
