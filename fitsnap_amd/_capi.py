@@ -127,6 +127,8 @@ SIGNATURES = {
                                  c_int64, c_void_p, c_void_p, c_void_p]),
     "fsnap_lasso_path": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_double, c_void_p,
                                  c_void_p, c_void_p]),
+    "fsnap_ard_path": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_double, c_void_p,
+                               c_void_p, c_void_p, c_void_p]),
     "fsnap_select_begin": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int]),
     "fsnap_select_pick": (c_int, [c_void_p, c_int, POINTER(ctypes.c_int32), POINTER(c_double)]),
     "fsnap_select_retire": (c_int, [c_void_p, ctypes.c_int32]),
@@ -1026,6 +1028,26 @@ class HipContext:
         self._check(self._lib.fsnap_lasso_path(self._h, K, F, int(nsub), c_void_p(d_stats_ptr), _ptr(alphas) if Q else None, Q,
                                                int(max_iter), float(tol), _ptr(coef), _ptr(info), _ptr(held)))
         return coef, info, held
+
+    def ard_path(self, d_stats_ptr: int, K: int, F: int, nsub: int, hyper, max_iter: int, tol: float):
+        """Grouped K-fold ARD threshold path on per-fold statistics in device memory (``fsnap_ard_path``, K <= 144):
+        ``d_stats_ptr`` as for ``lasso_path``; ``hyper`` ((F + 1) x Q x 6: alpha_1, alpha_2, lambda_1, lambda_2,
+        threshold_lambda, alpha_init of every problem).  Returns (coef ((F + 1) x Q x K; index F: no fold left out), lambdas
+        (the same shape), info ((F + 1) x Q x 6: iterations, kept columns, final alpha_, last sum |coef_old - coef|, smallest
+        pivot of the scaled matrices, status 0 converged or emptied / 1 failed / 2 max_iter reached), heldout (F x Q x 3: n_f,
+        weighted squared error of fold f under its own refit, bb_f))."""
+        hyper = _f64(hyper, "hyper")
+        K, F = int(K), int(F)
+        if hyper.ndim != 3 or hyper.shape[0] != max(F, 0) + 1 or hyper.shape[2] != 6:
+            raise ValueError(f"hyper must have shape (F + 1, Q, 6), not {hyper.shape}")
+        Q = hyper.shape[1]
+        coef = np.empty((max(F, 0) + 1, Q, max(K, 0)))
+        lam = np.empty((max(F, 0) + 1, Q, max(K, 0)))
+        info = np.empty((max(F, 0) + 1, Q, 6))
+        held = np.empty((max(F, 0), Q, 3))
+        self._check(self._lib.fsnap_ard_path(self._h, K, F, int(nsub), c_void_p(d_stats_ptr), _ptr(hyper) if Q else None, Q,
+                                             int(max_iter), float(tol), _ptr(coef), _ptr(lam), _ptr(info), _ptr(held)))
+        return coef, lam, info, held
 
     def lstsq_rows(self, rcond: float, K: int = None):
         """``lstsq(aw, bw, rcond)`` of the resident rows computed on the rows (fsnap_lstsq_rows); collective when the

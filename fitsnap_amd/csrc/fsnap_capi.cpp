@@ -2924,6 +2924,57 @@ int fsnap_lasso_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const d
     return FSNAP_OK;
 }
 
+// ---- grouped K-fold ARD threshold paths on the per-fold statistics (kernel S1 of fsnap_lasso.hip, A1 of fsnap_ard.hip) ----
+
+int fsnap_ard_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const double* d_stats, const double* hyper, int64_t Q,
+                   int64_t max_iter, double tol, double* coef_out, double* lambda_out, double* info_out, double* heldout_out) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_ard_path";
+    if (!d_stats || !hyper || !coef_out || !lambda_out || !info_out || !heldout_out)
+        return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
+    if (K < 1 || K > fsnap::ARD_MAX_K) return ctx->fail(FSNAP_E_ARG, "%s: K = %lld (1 ... %d)", who, (long long)K, fsnap::ARD_MAX_K);
+    if (F < 1 || nsub < 1 || F > 0x3FFFFFFF || nsub > 0x3FFFFFFF)
+        return ctx->fail(FSNAP_E_ARG, "%s: F = %lld, nsub = %lld", who, (long long)F, (long long)nsub);
+    if (Q < 1 || Q > 0xFFFFF || (F + 1) * Q > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: Q = %lld", who, (long long)Q);
+    if (max_iter < 1 || max_iter > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: max_iter = %lld", who, (long long)max_iter);
+    if (!std::isfinite(tol) || tol < 0.0) return ctx->fail(FSNAP_E_ARG, "%s: tol = %g is negative or not finite", who, tol);
+    const int64_t nprob = (F + 1) * Q;
+    for (int64_t i = 0; i < nprob * 6; ++i) {
+        const double h = hyper[i];
+        // entries 4 and 5 of a problem: threshold_lambda and alpha_init, both positive
+        if (!std::isfinite(h) || h < 0.0 || (i % 6 >= 4 && h <= 0.0))
+            return ctx->fail(FSNAP_E_ARG, "%s: hyper[%lld][%lld] = %g", who, (long long)(i / 6), (long long)(i % 6), h);
+    }
+    if (!cand_fits(F * nsub, K))
+        return ctx->fail(FSNAP_E_ARG, "%s: %lld blocks x %lld doubles exceed FSNAP_CAT_STATS_MAX_BYTES", who, (long long)(F * nsub),
+                         (long long)FSNAP_PACKED_LEN(K));
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    const int64_t T = FSNAP_PACKED_LEN(K);
+    const int64_t nfold = nsub > 1 ? F : 0;                 // nsub = 1: the caller's blocks are the folds
+    if (!ctx->lasso_sys.ensure((size_t)(nfold + 1) * T * 8) || !ctx->ard_hyper.ensure((size_t)nprob * 6 * 8) ||
+        !ctx->ard_coef.ensure((size_t)nprob * K * 8) || !ctx->ard_lambda.ensure((size_t)nprob * K * 8) ||
+        !ctx->ard_info.ensure((size_t)nprob * 6 * 8) || !ctx->ard_held.ensure((size_t)F * Q * 3 * 8))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(ard path) failed");
+    double* dfolds = nfold ? (double*)ctx->lasso_sys.p : nullptr;
+    double* dtotal = (double*)ctx->lasso_sys.p + nfold * T;
+    FSNAP_HIP(hipMemcpyAsync(ctx->ard_hyper.p, hyper, (size_t)nprob * 6 * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(hyper)");
+    FSNAP_HIP(fsnap::launch_lasso_folds(d_stats, (int)F, (int)nsub, (int)K, dfolds, dtotal, ctx->stream),
+              "launch fsnap_lasso_folds_k");
+    const int nblocks = (int)std::min<int64_t>(nprob, (int64_t)fsnap::ard_blocks_per_cu((int)K) * std::max(1, ctx->num_cu));
+    FSNAP_HIP(fsnap::launch_ard_path(nblocks, dfolds ? dfolds : d_stats, dtotal, (const double*)ctx->ard_hyper.p, (int)K, (int)F,
+                                     (int)Q, (int)max_iter, tol, (double*)ctx->ard_coef.p, (double*)ctx->ard_lambda.p,
+                                     (double*)ctx->ard_info.p, (double*)ctx->ard_held.p, ctx->stream),
+              "launch fsnap_ard_path_k");
+    FSNAP_HIP(hipMemcpyAsync(coef_out, ctx->ard_coef.p, (size_t)nprob * K * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(coef)");
+    FSNAP_HIP(hipMemcpyAsync(lambda_out, ctx->ard_lambda.p, (size_t)nprob * K * 8, hipMemcpyDeviceToHost, ctx->stream),
+              "hipMemcpy(lambda)");
+    FSNAP_HIP(hipMemcpyAsync(info_out, ctx->ard_info.p, (size_t)nprob * 6 * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(info)");
+    FSNAP_HIP(hipMemcpyAsync(heldout_out, ctx->ard_held.p, (size_t)F * Q * 3 * 8, hipMemcpyDeviceToHost, ctx->stream),
+              "hipMemcpy(heldout)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    return FSNAP_OK;                                        // a failed problem is its own status 1, not the call's
+}
+
 // ---- joint information-gain / variance-reduction scores of units (kernels J1, J2 of fsnap_joint.hip) ------------------
 
 namespace {

@@ -145,6 +145,9 @@ struct fsnap_ctx {
     DevBuf path_in, path_cls, path_base, path_sums, path_info, path_pred;
     // fsnap_lasso_path: [fold blocks (nsub > 1 only) | total], alphas, coefficients, info, held-out sums; kept between calls
     DevBuf lasso_sys, lasso_alphas, lasso_coef, lasso_info, lasso_held;
+    // fsnap_ard_path: hyper-parameters, coefficients, lambdas, info, held-out sums (the fold sums live in lasso_sys); kept
+    // between calls
+    DevBuf ard_hyper, ard_coef, ard_lambda, ard_info, ard_held;
     // fsnap_joint_*: the session's unit-sorted row index, unit offsets and per-position weights (uploaded once by begin), the
     // padded factor [M | M B] and B, Z / Pi per position (npos x Wp), the bucketed list of live units, per-unit (gain, reduction)
     // and info, per-workgroup scratch (S and the right-hand-side fragments of units too large for LDS); the host keeps the

@@ -267,6 +267,20 @@ int lasso_blocks_per_cu(int K);
 hipError_t launch_lasso_cd(int nblocks, const double* folds, const double* total, const double* alphas, int K, int F, int Q,
                            int max_iter, double tol, double* coef, double* info, double* heldout, hipStream_t st);
 
+// Grouped K-fold ARD threshold paths (fsnap_ard.hip; K <= ARD_MAX_K) on the folds and the total of kernel S1.  Kernel A1:
+// problem p = f Q + q (f = F: no fold left out) is ARD._ard_loop on (total - folds[f]) with hyper[p][6] = (alpha_1, alpha_2,
+// lambda_1, lambda_2, threshold_lambda, alpha_init), the inverse of every iteration from a Cholesky factor of the equilibrated
+// matrix of the kept columns and the residual sum of squares from the statistics; a column j with total G_jj = 0 or downdated
+// G_jj <= LOCO_PIVOT_TOL total G_jj is never kept.  coef[p][K], lambda[p][K], info[p][6] = (iterations, kept columns, final
+// alpha_, last sum |coef_old - coef|, smallest pivot, status 0 converged or emptied / 1 failed / 2 max_iter reached),
+// heldout[p][3] (p < F Q) = (n_f, bb_f - 2 beta . c_f + beta^T G_f beta, bb_f).  One workgroup of 256 threads per problem,
+// nblocks workgroups stride over the problems.  All pointers: device.
+constexpr int ARD_MAX_K = 144;
+size_t ard_lds_bytes(int K);
+int ard_blocks_per_cu(int K);
+hipError_t launch_ard_path(int nblocks, const double* folds, const double* total, const double* hyper, int K, int F, int Q,
+                           int max_iter, double tol, double* coef, double* lambda, double* info, double* heldout, hipStream_t st);
+
 // Joint unit scores (fsnap_joint.hip).  Kernel J1: for the npos positions of the unit-sorted row index idx,
 // ZP[p] = om[p] a_idx[p] [M | M B] (Wp doubles per position; Fp: device, Kp x Wp row-major, zero-padded: columns [0, Jp) the
 // factor M, columns [Jp, Wp) the target block M B; Wp = Jp without a target; om: the weight of every position).

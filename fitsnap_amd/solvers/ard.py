@@ -66,12 +66,21 @@ class ARD(Solver):
             self.fit = coef
 
     # sklearn 1.7.2 linear_model/_bayes.py ARDRegression.fit, on (G, c) instead of (X, y)
-    def _ard_loop(self, G, c, bb, n_samples, var_y, alpha_1, alpha_2, lambda_1, lambda_2, threshold_lambda, host_sse=None):
+    # ``live`` (columns that may ever be kept), ``tol`` / ``max_iter`` (default: the class constants), ``alpha_init`` (default
+    # 1 / (var_y + eps)) and ``probe`` serve solvers/ard_path.py; their defaults leave the loop, and its bits, as perform_fit
+    # runs it.  With a ``probe`` dict the loop reports into it -- "status" (0 converged or emptied, 1 failed, 2 max_iter
+    # reached), "delta" (the last sum |coef_old - coef|, against zeros in iteration 0), "pivot" (the smallest Cholesky pivot of
+    # the scaled matrices) -- and a scaled matrix that is not positive definite or a non-finite lambda ends it with status 1
+    # and NaN coefficients instead of being divided through.
+    def _ard_loop(self, G, c, bb, n_samples, var_y, alpha_1, alpha_2, lambda_1, lambda_2, threshold_lambda, host_sse=None,
+                  live=None, tol=None, max_iter=None, alpha_init=None, probe=None):
         K = len(c)
         eps = np.finfo(np.float64).eps
         coef_ = np.zeros(K)
-        keep = np.ones(K, dtype=bool)
-        alpha_ = 1.0 / (var_y + eps)
+        keep = np.ones(K, dtype=bool) if live is None else np.array(live, dtype=bool)
+        alpha_ = 1.0 / (var_y + eps) if alpha_init is None else float(alpha_init)
+        tol = self.TOL if tol is None else tol
+        max_iter = self.MAX_ITER if max_iter is None else max_iter
         lambda_ = np.ones(K)
         coef_old = None
 
@@ -87,7 +96,11 @@ class ARD(Solver):
         def update_sigma(alpha_, lambda_, keep):
             dk = dsc[keep]
             with blas_threads(len(dk)):         # (an eigh of <= K x K: the BLAS pool sized by the CPUs it sees takes 20 x longer)
-                scaled = pinvh(np.diag(lambda_[keep] / dk ** 2) + alpha_ * Gh[np.ix_(keep, keep)])
+                scaled = np.diag(lambda_[keep] / dk ** 2) + alpha_ * Gh[np.ix_(keep, keep)]
+                if probe is not None:
+                    piv = np.linalg.cholesky(scaled).diagonal() ** 2        # LinAlgError: not positive definite
+                    probe["pivot"] = min(probe.get("pivot", np.inf), float(piv.min()))
+                scaled = pinvh(scaled)
             return scaled / np.outer(dk, dk)
 
         def sse_of(coef_):
@@ -97,25 +110,48 @@ class ARD(Solver):
                 return self._device_sse(coef_)
             return float(bb - 2.0 * coef_ @ c + coef_ @ G @ coef_)
 
-        it = 0
-        for it in range(self.MAX_ITER):
-            sigma_ = update_sigma(alpha_, lambda_, keep)
-            coef_[keep] = alpha_ * (sigma_ @ c[keep])
-            sse_ = sse_of(coef_)
-            gamma_ = 1.0 - lambda_[keep] * np.diag(sigma_)
-            lambda_[keep] = (gamma_ + 2.0 * lambda_1) / (coef_[keep] ** 2 + 2.0 * lambda_2)
-            alpha_ = (n_samples - gamma_.sum() + 2.0 * alpha_1) / (sse_ + 2.0 * alpha_2)
-            keep = lambda_ < threshold_lambda
-            coef_[~keep] = 0
-            if it > 0 and np.sum(np.abs(coef_old - coef_)) < self.TOL:
-                break
-            coef_old = np.copy(coef_)
-            if not keep.any():
-                break
-        self.n_iter_ = it + 1
-        if keep.any():
-            sigma_ = update_sigma(alpha_, lambda_, keep)
-            coef_[keep] = alpha_ * (sigma_ @ c[keep])
+        n_iter, status = 0, 2
+        if probe is not None:
+            probe.update(status=0, delta=np.inf, pivot=np.inf)
+            coef_old = np.zeros(K)
+        try:
+            for it in range(max_iter if (live is None or keep.any()) else 0):
+                n_iter = it + 1
+                sigma_ = update_sigma(alpha_, lambda_, keep)
+                coef_[keep] = alpha_ * (sigma_ @ c[keep])
+                sse_ = sse_of(coef_)
+                gamma_ = 1.0 - lambda_[keep] * np.diag(sigma_)
+                lambda_[keep] = (gamma_ + 2.0 * lambda_1) / (coef_[keep] ** 2 + 2.0 * lambda_2)
+                alpha_ = (n_samples - gamma_.sum() + 2.0 * alpha_1) / (sse_ + 2.0 * alpha_2)
+                if probe is not None and not (np.all(np.isfinite(lambda_)) and np.isfinite(alpha_)):
+                    raise np.linalg.LinAlgError("non-finite lambda or alpha")
+                keep = lambda_ < threshold_lambda
+                if live is not None:
+                    keep &= live
+                coef_[~keep] = 0
+                if probe is not None:
+                    probe["delta"] = float(np.sum(np.abs(coef_old - coef_)))
+                if it > 0 and np.sum(np.abs(coef_old - coef_)) < tol:
+                    status = 0
+                    break
+                coef_old = np.copy(coef_)
+                if not keep.any():
+                    status = 0
+                    break
+            if n_iter == 0:
+                status = 0                      # no live column: nothing to iterate
+            self.n_iter_ = n_iter
+            if keep.any():
+                sigma_ = update_sigma(alpha_, lambda_, keep)
+                coef_[keep] = alpha_ * (sigma_ @ c[keep])
+        except np.linalg.LinAlgError:
+            if probe is None:
+                raise
+            self.n_iter_ = n_iter
+            status = 1
+            coef_ = np.full(K, np.nan)
+        if probe is not None:
+            probe["status"] = status
         self.lambda_, self.alpha_ = lambda_, alpha_
         return coef_
 

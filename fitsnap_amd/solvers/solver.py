@@ -25,7 +25,7 @@ import numpy as np
 
 from .. import _capi
 from .._hostblas import blas_threads
-from . import lasso_path, loco, ridge_path, select, select_joint, uq
+from . import ard_path, lasso_path, loco, ridge_path, select, select_joint, uq
 
 
 class _TrainWeights:
@@ -1194,3 +1194,31 @@ class Solver:
         the minimum (ties to the larger alpha) and ``sparsest`` that of the largest alpha within one ``cv_se`` of it.
         Neither the fit nor the config is changed.  Raises ValueError for other solvers and for ``apply_transpose``."""
         return lasso_path.lasso_path(self, alphas, folds, by, fs_dict, b, w, tol, max_iter, method, table, seed)
+
+    # ------------------------------------------------------------------------------
+    # grouped K-fold ARD threshold paths (solvers/ard_path.py, csrc/fsnap_ard.hip)
+    # ------------------------------------------------------------------------------
+    def ard_path(self, grid, folds=5, by="Configs", fs_dict=None, b=None, w=None, tol=None, max_iter=None, method="auto",
+                 table="auto", seed=0):
+        """Grouped K-fold cross-validation of the ARD fit over a grid of ``[ARD]`` settings, after ``perform_fit`` of an ARD
+        solver, from ONE pass over the resident training rows: the units (``fs_dict[by]``, as in ``loco_errors``) are dealt
+        into folds as in ``lasso_path``, the statistics of every fold are formed on the GPU and every (fold left out, setting)
+        refit plus the fit on all rows per setting runs ``ARD._ard_loop``'s iteration on "total minus fold", with the
+        hyper-parameters ``perform_fit`` would compute on the rows that remain.  ``grid``: a sequence of mappings that
+        override ``logcut``, ``scap``, ``scai`` (under ``directmethod``: ``threshold_lambda``, ``alphabig``, ``lambdasmall``);
+        a sequence of numbers stands for ``logcut`` (``threshold_lambda``) values.  ``tol`` defaults to ``ARD.TOL``,
+        ``max_iter`` to ``ARD.MAX_ITER``.  ``method``: "device" (the kernel, K <= 144; the inverse of an iteration from a
+        Cholesky factor), "host" (``_ard_loop`` with ``pinvh`` over the downloaded fold statistics) or "auto" (the kernel
+        where it exists).  Both differ from ``perform_fit`` in the residual sum of squares of an iteration, which is the
+        statistics form y2 - 2 coef . qv + coef^T Qm coef (1e-8 in the coefficients on the Ta rows).  ``folds``, ``table``,
+        labels, truths and weights as in ``lasso_path``; the table is keyed (setting, Row_Type) by the position in the grid.
+        Collective on several ranks; a unit may span ranks.
+        Returns ``ArdPath(grid, fits, lambdas, nonzeros, iterations, status, alpha_, table, fold_of_unit, cv_error, cv_se,
+        best, best_setting, sparsest, sparsest_setting)``: the resolved settings; the Q x K fits on all training rows, their
+        lambdas and non-zero counts; iterations, status (0 converged or emptied, 1 failed, 2 ``max_iter`` reached) and final
+        alpha_ ((F + 1) x Q, row F the fits on all rows); ``cv_error`` the pooled weighted held-out mean squared error per
+        setting (NaN where a problem of the setting failed) and ``cv_se`` its standard error over the folds; ``best`` the index
+        of the minimum (ties to fewer non-zeros, then the lower index) and ``sparsest`` that of the fewest non-zeros within one
+        ``cv_se`` of it.  Neither the fit nor the config is changed.  Raises ValueError for other solvers, for
+        ``apply_transpose``, for an empty grid and for unknown grid keys."""
+        return ard_path.ard_path(self, grid, folds, by, fs_dict, b, w, tol, max_iter, method, table, seed)

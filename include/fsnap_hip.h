@@ -403,6 +403,32 @@ int fsnap_ridge_path(fsnap_ctx* ctx, int64_t K, const double* G, const double* c
 int fsnap_lasso_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const double* d_stats, const double* alphas, int64_t Q,
                      int64_t max_iter, double tol, double* coef_out, double* info_out, double* heldout_out);
 
+/* Grouped K-fold ARD threshold paths on per-fold statistics (kernel S1 of csrc/fsnap_lasso.hip, A1 of csrc/fsnap_ard.hip;
+ * the grid, the hyper-parameters, the host route and the picks are solvers/ard_path.py).  d_stats (DEVICE), the folds and the
+ * total T as for fsnap_lasso_path.  Problem (f, q), f < F: the refit without fold f; f = F: the fit on all training rows:
+ *     Qm = T.G - G_f,  qv = T.c - c_f,  y2 = T.bb - bb_f,  n = T.n - n_f                                 (f = F: T alone)
+ *     hyper[f][q] = (alpha_1, alpha_2, lambda_1, lambda_2, threshold_lambda, alpha_init)              (host, (F + 1) x Q x 6)
+ * Column j is dead -- never kept, coefficient 0 -- when T.G_jj == 0 or Qm_jj <= 1e-10 T.G_jj; d_j = sqrt(Qm_jj) (1 for a dead
+ * column).  The iteration is scikit-learn's ARDRegression.fit on the statistics (solvers/ard.py, ARD._ard_loop), from coef = 0,
+ * lambda = 1, keep = the live columns, alpha_ = alpha_init; per iteration Sigma = D^-1 W^-1 D^-1 with W = diag(lambda_k / d_k^2)
+ * + alpha_ Qm[keep, keep] / (d d^T) = L L^T (a Cholesky factor, inverted in place), coef[keep] = alpha_ Sigma qv[keep], sse =
+ * max(y2 - 2 coef . qv + coef^T Qm coef, 0), gamma = 1 - lambda_k Sigma_kk, lambda_k = (gamma + 2 lambda_1) / (coef_k^2 + 2
+ * lambda_2), alpha_ = (n - sum gamma + 2 alpha_1) / (sse + 2 alpha_2), keep = lambda < threshold_lambda with the pruned
+ * coefficients zeroed; it stops after the second or a later iteration when sum |coef_old - coef| < tol, when keep is empty, or
+ * at max_iter, and recomputes Sigma and coef once more when keep is not empty.  A problem without a live column runs no
+ * iteration.  A pivot that is not positive or a lambda or alpha_ that is not finite ends the problem with status 1 and NaN
+ * coefficients and lambdas; the call still returns FSNAP_OK.  Outputs (host): coef_out, lambda_out[(F + 1)][Q][K];
+ * info_out[(F + 1)][Q][6] = iterations, kept columns, final alpha_, the last sum |coef_old - coef| (against zeros in the first
+ * iteration; inf before any), the smallest pivot of W over all iterations (inf before any), status (0 converged or emptied,
+ * 1 failed, 2 max_iter reached); heldout_out[F][Q][3] = n_f, bb_f - 2 beta . c_f + beta^T G_f beta (the weighted squared error
+ * of fold f under its own refit), bb_f.  FSNAP_E_ARG for K outside 1 ... 144, F < 1, nsub < 1, Q < 1, max_iter < 1, a negative
+ * or non-finite tol or hyper entry, threshold_lambda <= 0, alpha_init <= 0, a NULL pointer, or F * nsub blocks past
+ * FSNAP_CAT_STATS_MAX_BYTES.  fp64, no atomics; every sum runs in an order that depends on the problem alone: bit-identical run
+ * to run and under any permutation or subset of the grid.  The resident rows, weights, mask and category layout are not
+ * touched.  Synchronous. */
+int fsnap_ard_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const double* d_stats, const double* hyper, int64_t Q,
+                   int64_t max_iter, double tol, double* coef_out, double* lambda_out, double* info_out, double* heldout_out);
+
 /* Joint scores of units (normally configurations) of the resident rows for active learning (kernels J1, J2 of
  * csrc/fsnap_joint.hip, fp64 MFMA; the host algebra is solvers/select_joint.py).  With the posterior C = M M^T (M: K x J),
  * the noise variance tau of a unit-weight row, the weighted rows X_u = diag(omega) A_u (n_u x K) of unit u, Z = X_u M and a
