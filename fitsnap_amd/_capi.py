@@ -123,6 +123,8 @@ SIGNATURES = {
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fsnap_loco_rows": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                 c_void_p]),
+    "fsnap_loco_rows_uq": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                   c_void_p, c_void_p]),
     "fsnap_ridge_path": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
                                  c_int64, c_void_p, c_void_p, c_void_p]),
     "fsnap_lasso_path": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_double, c_void_p,
@@ -955,11 +957,8 @@ class HipContext:
         """Drop the joint-score session (``fsnap_joint_end``)."""
         self._check(self._lib.fsnap_joint_end(self._h))
 
-    def loco_rows(self, M, beta, sorted_rows, cfg_offsets):
-        """Leave-one-configuration-out predictions of the resident training rows (``fsnap_loco_rows``): M (K x J) with
-        C = M M^T, the fit ``beta`` (K), the rows of configuration c at ``sorted_rows[cfg_offsets[c]:cfg_offsets[c + 1]]``.
-        Returns (pred (m, NaN where a row is not listed or its configuration is not identifiable), info (ncfg x 4:
-        d_c, smallest pivot, identifiable, n space))."""
+    def _loco_args(self, M, beta, sorted_rows, cfg_offsets):
+        """(M, beta, rows, offsets, K, J, ncfg) of ``loco_rows`` / ``loco_rows_uq``, checked."""
         M = _f64(M, "M")
         if M.ndim == 1:
             M = M.reshape(-1, 1)
@@ -976,11 +975,31 @@ class HipContext:
         ncfg = off.size - 1
         if off[-1] != rows.size:
             raise ValueError(f"cfg_offsets ends at {off[-1]}, sorted_rows has {rows.size} entries")
+        return M, beta, rows, off, K, J, ncfg
+
+    def loco_rows(self, M, beta, sorted_rows, cfg_offsets):
+        """Leave-one-configuration-out predictions of the resident training rows (``fsnap_loco_rows``): M (K x J) with
+        C = M M^T, the fit ``beta`` (K), the rows of configuration c at ``sorted_rows[cfg_offsets[c]:cfg_offsets[c + 1]]``.
+        Returns (pred (m, NaN where a row is not listed or its configuration is not identifiable), info (ncfg x 4:
+        d_c, smallest pivot, identifiable, n space))."""
+        M, beta, rows, off, K, J, ncfg = self._loco_args(M, beta, sorted_rows, cfg_offsets)
         pred = np.empty(self.m)
         info = np.empty((ncfg, 4))
         self._check(self._lib.fsnap_loco_rows(self._h, K, J, _ptr(M), _ptr(beta), _ptr(rows) if rows.size else None,
                                               _ptr(off), ncfg, _ptr(pred), _ptr(info)))
         return pred, info
+
+    def loco_rows_uq(self, M, beta, sorted_rows, cfg_offsets):
+        """``loco_rows`` with the leave-out predictive variances (``fsnap_loco_rows_uq``).  Returns (pred, as ``loco_rows``
+        bit for bit; leverage (m: q_i = a_i (G - X_c^T X_c + alpha I)^-1 a_i^T, NaN as pred); info (ncfg x 6: d_c, smallest
+        pivot, identifiable, n space, log det H_c, e_c^T H_c^-1 e_c))."""
+        M, beta, rows, off, K, J, ncfg = self._loco_args(M, beta, sorted_rows, cfg_offsets)
+        pred = np.empty(self.m)
+        lev = np.empty(self.m)
+        info = np.empty((ncfg, 6))
+        self._check(self._lib.fsnap_loco_rows_uq(self._h, K, J, _ptr(M), _ptr(beta), _ptr(rows) if rows.size else None,
+                                                 _ptr(off), ncfg, _ptr(pred), _ptr(lev), _ptr(info)))
+        return pred, lev, info
 
     def ridge_path(self, G, c, alphas, sorted_rows, unit_offsets, row_class, nclass, want_preds=False):
         """Leave-one-unit-out refits of the resident training rows over a grid of alphas (``fsnap_ridge_path``, K <= 144): the

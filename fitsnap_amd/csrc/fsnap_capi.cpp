@@ -2793,6 +2793,103 @@ int fsnap_loco_rows(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, const
     return FSNAP_OK;
 }
 
+// ---- leave-one-configuration-out leverages, log-determinants and joint distances (kernels L1 of fsnap_loco.hip and L3 of
+// fsnap_loco_uq.hip); fsnap_loco_rows's arguments, checks and predictions -----------------------------------------------
+
+int fsnap_loco_rows_uq(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, const double* beta, const int32_t* sorted_rows,
+                       const int64_t* cfg_offsets, int64_t ncfg, double* pred_out, double* lev_out, double* cfg_info_out) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_loco_rows_uq";
+    if (!M || !beta || !cfg_offsets || !pred_out || !lev_out || (ncfg > 0 && !cfg_info_out))
+        return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
+    if (K < 1 || K > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: K = %lld", who, (long long)K);
+    if (J < 1 || J > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: J = %lld", who, (long long)J);
+    if (ncfg < 0 || ncfg > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: ncfg = %lld", who, (long long)ncfg);
+    const int64_t m = ctx->m;
+    if (m > 0 && K != ctx->K)
+        return ctx->fail(FSNAP_E_ARG, "%s: K = %lld, the resident rows have %lld columns", who, (long long)K, (long long)ctx->K);
+    if (m > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: needs m < 2^31", who);
+    int rc = check_unit_index(ctx, who, "cfg_offsets", sorted_rows, cfg_offsets, ncfg, m, [](int64_t, int32_t) { return 0; });
+    if (rc) return rc;
+    const int64_t npos = cfg_offsets[ncfg];
+    for (int64_t i = 0; i < m; ++i) pred_out[i] = lev_out[i] = std::numeric_limits<double>::quiet_NaN();
+    for (int64_t c = 0; c < ncfg; ++c) {      // empty configurations: nothing to leave out
+        cfg_info_out[6 * c] = 0.0;
+        cfg_info_out[6 * c + 1] = std::numeric_limits<double>::infinity();
+        cfg_info_out[6 * c + 2] = 1.0;
+        cfg_info_out[6 * c + 3] = 1.0;
+        cfg_info_out[6 * c + 4] = 0.0;      // log det and distance of nothing
+        cfg_info_out[6 * c + 5] = 0.0;
+    }
+    if (npos == 0) return FSNAP_OK;
+    if ((rc = check_rows(ctx)) || (rc = check_weights(ctx))) return rc;
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    if (ctx->uq_inflight) {
+        FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+        ctx->uq_inflight = false;
+    }
+    int npk = 0;
+    if ((rc = ensure_wpack(ctx, &npk))) return rc;
+    const double* wpack = ctx->wpack_override ? ctx->wpack_override : (const double*)ctx->wpack.p;
+    // configurations by solve size d_c = min(n_c, J); general path: one (dmax^2 + 3 dmax) slice of scratch per workgroup
+    const UnitBins bins = bin_units(
+        ncfg, [&](int64_t c) { return cfg_offsets[c + 1] - cfg_offsets[c]; }, J, fsnap::LOCO_MAX_LDS_D, ctx->num_cu,
+        [](int64_t dmax) { return dmax * dmax + 3 * dmax; }, ctx->loco_hlist);
+    const int64_t dmax = bins.dmax, hslice = dmax * dmax + 3 * dmax;
+    const int* nblk = bins.nblk;
+    const int64_t Kp = (K + 15) / 16 * 16, Jp = (J + 15) / 16 * 16;
+    const size_t nM = (size_t)(Kp * Jp);
+    ctx->loco_hM.assign(nM + (size_t)Kp, 0.0);
+    for (int64_t k = 0; k < K; ++k) std::memcpy(&ctx->loco_hM[(size_t)(k * Jp)], M + k * J, (size_t)J * 8);
+    std::memcpy(&ctx->loco_hM[nM], beta, (size_t)K * 8);
+    const int nvg = std::max({nblk[0], nblk[1], nblk[2], nblk[3], 1});
+    if (!ctx->loco_M.ensure((nM + (size_t)Kp) * 8) || !ctx->loco_idx.ensure((size_t)npos * 4) ||
+        !ctx->loco_off.ensure((size_t)(ncfg + 1) * 8) || !ctx->loco_list.ensure(std::max<size_t>(ctx->loco_hlist.size(), 1) * 4) ||
+        !ctx->loco_Z.ensure((size_t)npos * (size_t)Jp * 8) || !ctx->loco_aux.ensure((size_t)npos * 3 * 8) ||
+        !ctx->loco_pred.ensure((size_t)m * 8) || !ctx->loco_lev.ensure((size_t)m * 8) ||
+        !ctx->loco_info.ensure((size_t)ncfg * 6 * 8) ||
+        !ctx->loco_v.ensure((size_t)nvg * (size_t)Jp * 8) || (nblk[3] > 0 && !ctx->loco_H.ensure((size_t)nblk[3] * (size_t)hslice * 8)))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(loco) failed");
+    FSNAP_HIP(hipMemcpyAsync(ctx->loco_M.p, ctx->loco_hM.data(), (nM + (size_t)Kp) * 8, hipMemcpyHostToDevice, ctx->stream),
+              "hipMemcpy(M)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->loco_idx.p, sorted_rows, (size_t)npos * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(idx)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->loco_off.p, cfg_offsets, (size_t)(ncfg + 1) * 8, hipMemcpyHostToDevice, ctx->stream),
+              "hipMemcpy(offsets)");
+    if (!ctx->loco_hlist.empty())
+        FSNAP_HIP(hipMemcpyAsync(ctx->loco_list.p, ctx->loco_hlist.data(), ctx->loco_hlist.size() * 4, hipMemcpyHostToDevice,
+                                 ctx->stream),
+                  "hipMemcpy(lists)");
+    FSNAP_HIP(hipMemsetAsync(ctx->loco_pred.p, 0xFF, (size_t)m * 8, ctx->stream), "hipMemset(pred)");   // all-ones: NaN
+    FSNAP_HIP(hipMemsetAsync(ctx->loco_lev.p, 0xFF, (size_t)m * 8, ctx->stream), "hipMemset(lev)");
+    double* aux = (double*)ctx->loco_aux.p;
+    FSNAP_HIP(fsnap::launch_loco_zeta(ctx->dA, ctx->lda, (int)K, (const int*)ctx->loco_idx.p, npos, wpack,
+                                      (const double*)ctx->loco_M.p, (int)Jp, (const double*)ctx->loco_M.p + nM,
+                                      (double*)ctx->loco_Z.p, aux, aux + npos, aux + 2 * npos, ctx->stream),
+              "launch fsnap_loco_zeta_k");
+    size_t first = 0;
+    for (int b = 0; b < 4; ++b) {
+        const int ncl = (int)bins.lists[b].size();
+        if (ncl > 0)
+            FSNAP_HIP(fsnap::launch_loco_uq_cfg(bins.D[b], nblk[b], (const double*)ctx->loco_Z.p, (int)Jp, (int)J, aux,
+                                                aux + npos, aux + 2 * npos, (const int*)ctx->loco_idx.p,
+                                                (const int64_t*)ctx->loco_off.p, (const int*)ctx->loco_list.p + first, ncl,
+                                                (double*)ctx->loco_H.p, (int)dmax, (double*)ctx->loco_v.p,
+                                                (double*)ctx->loco_pred.p, (double*)ctx->loco_lev.p,
+                                                (double*)ctx->loco_info.p, ctx->stream),
+                      "launch fsnap_loco_uq_cfg_k");
+        first += (size_t)ncl;
+    }
+    ctx->loco_hinfo.resize((size_t)ncfg * 6);
+    FSNAP_HIP(hipMemcpyAsync(pred_out, ctx->loco_pred.p, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(pred)");
+    FSNAP_HIP(hipMemcpyAsync(lev_out, ctx->loco_lev.p, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(lev)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->loco_hinfo.data(), ctx->loco_info.p, (size_t)ncfg * 48, hipMemcpyDeviceToHost, ctx->stream),
+              "hipMemcpy(info)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    for (int64_t c = 0; c < ncfg; ++c)
+        if (cfg_offsets[c + 1] > cfg_offsets[c]) std::memcpy(cfg_info_out + 6 * c, &ctx->loco_hinfo[(size_t)(6 * c)], 48);
+    return FSNAP_OK;
+}
+
 // ---- leave-one-unit-out refits over a grid of alphas (kernel P1 of fsnap_path.hip) ---------------------------------------
 
 int fsnap_ridge_path(fsnap_ctx* ctx, int64_t K, const double* G, const double* c, const double* alphas, int64_t Q,

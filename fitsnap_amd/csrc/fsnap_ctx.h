@@ -138,6 +138,7 @@ struct fsnap_ctx {
     // (npos x Jp), (w, e, a . beta) per position, per-row predictions, per-configuration info, per-workgroup scratch (v; H of
     // the configurations too large for LDS); kept between calls like the other workspaces
     DevBuf loco_M, loco_idx, loco_off, loco_list, loco_Z, loco_aux, loco_pred, loco_info, loco_v, loco_H;
+    DevBuf loco_lev;                   // fsnap_loco_rows_uq: the leverage per row (its other buffers are those above)
     std::vector<double> loco_hM, loco_hinfo;
     std::vector<int32_t> loco_hlist;
     // fsnap_ridge_path: [G | c | alphas], row classes, per-workgroup base tiles, sums, info, predictions (the unit index and

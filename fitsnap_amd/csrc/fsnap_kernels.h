@@ -236,6 +236,13 @@ constexpr double LOCO_PIVOT_TOL = 1e-10;     // pivots of I - S_c (diagonal <= 1
 hipError_t launch_loco_cfg(int D, int nblocks, const double* Z, int Jp, int J, const double* pw, const double* pe,
                            const double* pb, const int* idx, const int64_t* off, const int* clist, int ncl, double* Hg,
                            int dmax, double* vg, double* pred, double* info, hipStream_t st);
+// Kernel L3 (fsnap_loco_uq.hip): launch_loco_cfg's geometry and predictions (bit for bit), plus lev[idx[p]] = the leave-out
+// leverage q_i of every row (NaN for a configuration that is not identifiable) and info[6 c ..] = (d_c, smallest pivot,
+// identifiable, n space, log det H_c, e_c^T H_c^-1 e_c; the last two NaN when not identifiable).  D = 0: Hg holds
+// nblocks x (dmax^2 + 3 dmax) doubles.
+hipError_t launch_loco_uq_cfg(int D, int nblocks, const double* Z, int Jp, int J, const double* pw, const double* pe,
+                              const double* pb, const int* idx, const int64_t* off, const int* clist, int ncl, double* Hg,
+                              int dmax, double* vg, double* pred, double* lev, double* info, hipStream_t st);
 
 // Leave-one-unit-out refits over a grid of alphas (fsnap_path.hip, kernel P1; K <= PATH_MAX_K).  For every unit u (positions
 // off[u] .. off[u + 1] of idx) and alpha_q: beta = (G - G_u + alpha_q I)^-1 (c - c_u) by a Jacobi-scaled blocked Cholesky,

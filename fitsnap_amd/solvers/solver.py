@@ -25,7 +25,7 @@ import numpy as np
 
 from .. import _capi
 from .._hostblas import blas_threads
-from . import ard_path, lasso_path, loco, ridge_path, select, select_joint, uq
+from . import ard_path, lasso_path, loco, loco_uq, ridge_path, select, select_joint, uq
 
 
 class _TrainWeights:
@@ -1147,6 +1147,29 @@ class Solver:
         max |LOO residual|, identifiable, d, smallest pivot) and the number of units that are not identifiable.
         Raises ValueError for solvers whose fit is not a linear smoother of the rows and for ``apply_transpose``."""
         return loco.loco_errors(self, by, fs_dict, b, w)
+
+    # ------------------------------------------------------------------------------
+    # leave-one-configuration-out predictive variances and calibration (solvers/loco_uq.py, csrc/fsnap_loco_uq.hip)
+    # ------------------------------------------------------------------------------
+    def loco_predictive(self, by="Configs", fs_dict=None, b=None, w=None, noise=None, method="auto"):
+        """Is the predicted uncertainty right?  Every training row is predicted by the posterior that has never seen its
+        unit (``fs_dict[by]``, as in ``loco_errors``: same labels, truths, weights, solvers and factor), and its residual
+        is compared with the predictive variance of THAT posterior, sigma^2 (1 / w_i^2 + q_i) with the leave-out leverage
+        q_i = a_i (G - X_c^T X_c + alpha I)^-1 a_i^T -- exact, without refits, on the GPU from the resident training rows.
+        ``noise``: sigma^2 of a unit-weight row; None takes ``sigmahat`` (ANL) or the weighted residual sum of squares of
+        the fit over n_train - tr(G C) (SVD / RIDGE).  ``method``: "device" (``fsnap_loco_rows_uq``), "host" (the same
+        closed form in numpy on the downloaded rows) or "auto" (device).  Collective on several ranks; every unit must
+        live on one rank; the factor, the fit and the noise are rank 0's.  Returns ``loco_uq.LocoPredictive(pred,
+        leverage, var, z, units, tables, summary, noise)``: per-row arrays of this rank's rows (``pred`` is
+        ``loco_errors().preds`` bit for bit; NaN on testing rows and unidentifiable units, ``var`` and ``z`` also where
+        w = 0), a DataFrame with one row per unit (label, group, rows, rows with w > 0, d, identifiable, D_c / sigma^2,
+        log det H_c, joint log density of the unit's targets), and on rank 0 (None elsewhere) a DataFrame per (Group,
+        Row_Type) with ``*ALL`` rows (n, mean z^2, share of |z| <= 1 and <= 2 next to the nominal 0.6827 / 0.9545, mean
+        marginal negative log density) and a dict (``logdens``: the total leave-out log predictive density, ``mean_z2``,
+        ``calibrated_noise``: sum D_c / sum n'_c, the sigma^2 at which the joint chi^2 matches its degrees of freedom,
+        ``units``, ``unidentifiable``).  Raises ValueError for solvers whose fit is not a linear smoother of the rows,
+        for ``apply_transpose`` and when the noise cannot be resolved (no degrees of freedom left)."""
+        return loco_uq.loco_predictive(self, by, fs_dict, b, w, noise, method)
 
     # ------------------------------------------------------------------------------
     # leave-one-configuration-out error over a grid of ridge alphas (solvers/ridge_path.py, csrc/fsnap_path.hip)

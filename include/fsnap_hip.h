@@ -364,6 +364,24 @@ int fsnap_select_end(fsnap_ctx* ctx);
 int fsnap_loco_rows(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, const double* beta, const int32_t* sorted_rows,
                     const int64_t* cfg_offsets, int64_t ncfg, double* pred_out, double* cfg_info_out);
 
+/* Leave-one-configuration-out predictive variances next to the predictions (kernel L1 of csrc/fsnap_loco.hip, kernel L3 of
+ * csrc/fsnap_loco_uq.hip, fp64 MFMA; no refit).  Arguments, checks and error codes are those of fsnap_loco_rows, and pred_out
+ * is what fsnap_loco_rows writes for the same inputs, bit for bit.  With H_c = I - Z_c Z_c^T (n space, n_c <= J) or
+ * I - Z_c^T Z_c (J space) = L L^T, the matrix whose inverse is the predictive covariance of the configuration's weighted
+ * rows under the fit without c, in units of the noise:
+ *     lev_out[i] = q_i = a_i (G - X_c^T X_c + alpha I)^-1 a_i^T      for every row i of c (also where w_i = 0)
+ *                = |L^-1 zeta_i^T|^2  (J space)  =  |zeta_i|^2 + |L^-1 Z_c zeta_i^T|^2  (n space)
+ *     Var(w_i b_i - w_i pred_i) = sigma^2 (1 + w_i^2 q_i)            with sigma^2 the noise variance of a unit-weight row
+ * lev_out: m doubles (NaN for rows that are not listed, and for every row of a configuration that is not identifiable);
+ * cfg_info_out: ncfg x 6 doubles (d_c = min(n_c, J), smallest Cholesky pivot, identifiable 1 / 0, n space 1 / 0,
+ * l_c = log det H_c = 2 sum log L_kk, D_c = e_c^T H_c^-1 e_c; l_c and D_c are NaN for a configuration that is not
+ * identifiable; a configuration without rows gets (0, inf, 1, 1, 0, 0)).  The joint log density of the configuration's
+ * weighted targets is -1/2 [n' log(2 pi sigma^2) - l_c + D_c / sigma^2], n' the rows with w_i > 0.  Every sum runs in an order
+ * that depends on the configuration's own rows alone: bit-identical run to run and under any permutation or subset of the
+ * configurations; no atomics.  Host in and out, synchronous. */
+int fsnap_loco_rows_uq(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, const double* beta, const int32_t* sorted_rows,
+                       const int64_t* cfg_offsets, int64_t ncfg, double* pred_out, double* lev_out, double* cfg_info_out);
+
 /* Exact leave-one-unit-out errors of ridge fits over a grid of alphas from the resident training rows (kernel P1 of
  * csrc/fsnap_path.hip, fp64 MFMA; K <= 144).  G (host, K x K row-major; the lower triangle is read) and c (host, K) are the
  * statistics of the weighted rows x_i = w_i a_i, y_i = w_i b_i (w_i = 0 off the mask), alphas (host, Q doubles, finite, >= 0)
