@@ -101,6 +101,8 @@ SIGNATURES = {
     "fsnap_dev_download": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
     "fsnap_lstsq_rows": (c_int, [c_void_p, c_double, c_int64, c_void_p, POINTER(c_int), c_void_p]),
     "fsnap_set_dense_pinv": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "fsnap_trsm_pass": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, POINTER(c_int)]),
+    "fsnap_qpack_device": (c_int, [c_void_p, c_void_p]),
     "fsnap_rowspace_factor": (c_int, [c_int64, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p]),
     "fsnap_rowspace_solve": (c_int, [c_int64, c_void_p, c_void_p, c_double, c_void_p, POINTER(c_int), c_void_p]),
     "fsnap_timing": (c_int, [c_void_p, _P_D, c_int]),
@@ -1067,6 +1069,22 @@ class HipContext:
         self._check(self._lib.fsnap_ard_path(self._h, K, F, int(nsub), c_void_p(d_stats_ptr), _ptr(hyper) if Q else None, Q,
                                              int(max_iter), float(tol), _ptr(coef), _ptr(lam), _ptr(info), _ptr(held)))
         return coef, lam, info, held
+
+    def trsm_pass(self, R, first: bool, d_Q_ptr: int, family: int = 0):
+        """One pass Q <- X R^-1 (fsnap_trsm_pass): ``R`` K x K upper triangular on the host; ``first``: X = diag(w_eff) A of
+        the resident rows written to the device buffer at ``d_Q_ptr`` (m x K, contiguous), else in place on that buffer;
+        ``family`` 0 = the kernel lstsq_rows picks, 1 = kernel 13C, 2 / 3 = kernel 13B with 16- / 32-row tiles.  Returns the
+        family that ran."""
+        R = _f64(R, "R")
+        if R.shape != (self.K, self.K):
+            raise ValueError(f"R has shape {R.shape}, expected ({self.K}, {self.K})")
+        ran = c_int(0)
+        self._check(self._lib.fsnap_trsm_pass(self._h, _ptr(R), int(bool(first)), int(family), c_void_p(d_Q_ptr), byref(ran)))
+        return ran.value
+
+    def qpack_device(self, d_qpack_ptr: int):
+        """(w_eff != 0, w_eff b) per resident row into the device buffer at ``d_qpack_ptr`` (2 m doubles)."""
+        self._check(self._lib.fsnap_qpack_device(self._h, c_void_p(d_qpack_ptr)))
 
     def lstsq_rows(self, rcond: float, K: int = None):
         """``lstsq(aw, bw, rcond)`` of the resident rows computed on the rows (fsnap_lstsq_rows); collective when the

@@ -749,7 +749,7 @@ int normal_eq_launch_on(fsnap_ctx* ctx, const double* Q, int64_t ldq, const doub
 
 extern "C" {
 
-int fsnap_version(void) { return 200; }
+int fsnap_version(void) { return 201; }
 
 int fsnap_device_count(int* count) {
     if (!count) return FSNAP_E_ARG;

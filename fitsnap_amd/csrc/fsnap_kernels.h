@@ -328,6 +328,14 @@ inline void trsm_invert_diagonal_blocks(double* Rpad, int K16) {
 }
 hipError_t launch_trsm_rows(const double* src, int64_t lds, const double* wpack, double* Q, int64_t ldq, int64_t m, int K,
                             const double* R, int K16, hipStream_t st);
+// launch_trsm_rows = trsm_family (the rule that picks the kernel from the shape) + launch_trsm_family (the launcher of a
+// named family: kernel 13C, K16 <= 144; kernel 13B with 16-row tiles (TR = 1, KG = 64) or 32-row tiles (TR = 2, KG = 16),
+// K16 > 128).  A family that the rule can never pick at K16 is refused (hipErrorInvalidValue).  fsnap_trsm_pass hands the
+// tests a single pass of a named family.
+enum : int { TRSM_ACC2 = 1, TRSM_PANEL16 = 2, TRSM_PANEL32 = 3 };
+int trsm_family(int64_t m, int K16);
+hipError_t launch_trsm_family(int family, const double* src, int64_t lds, const double* wpack, double* Q, int64_t ldq, int64_t m,
+                              int K, const double* R, int K16, hipStream_t st);
 // qpack[row] = (w_eff != 0 ? 1 : 0, w_eff b): per-row pairs that make the SYRK kernels compute Q^T Q and Q^T (w b)
 hipError_t launch_qpack(const double* wpack, int64_t m, double* qpack, hipStream_t st);
 

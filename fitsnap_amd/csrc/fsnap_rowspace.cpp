@@ -200,6 +200,54 @@ int fsnap_set_dense_pinv(fsnap_ctx* ctx, fsnap_dense_pinv_fn fn, void* user) {
     return FSNAP_OK;
 }
 
+int fsnap_trsm_pass(fsnap_ctx* ctx, const double* R, int first, int family, double* d_Q, int* family_run) {
+    if (!ctx) return FSNAP_E_ARG;
+    if (!R || !d_Q || family < 0 || family > 3 || (first != 0 && first != 1)) return ctx->fail(FSNAP_E_ARG, "fsnap_trsm_pass: bad argument");
+    if (!ctx->dA || ctx->m <= 0) return ctx->fail(FSNAP_E_STATE, "no rows: call fsnap_upload_rows/fsnap_bind_rows first");
+    if (ctx->K > (1 << 14)) return ctx->fail(FSNAP_E_ARG, "fsnap_trsm_pass: K = %lld", (long long)ctx->K);
+    const int K = (int)ctx->K, K16 = (K + 15) & ~15;
+    const int fam = family ? family : fsnap::trsm_family(ctx->m, K16);
+    // a kernel that fsnap_lstsq_rows can never launch at this width is not run here either
+    if (fam == fsnap::TRSM_ACC2 ? K16 > 144 : K16 <= 128)
+        return ctx->fail(FSNAP_E_ARG, "fsnap_trsm_pass: family %d does not run at K = %d", fam, K);
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    int rc;
+    if (first && (rc = fsnap::wpack_current(ctx))) return rc;
+    if (!ctx->rowspace) {
+        ctx->rowspace = new (std::nothrow) fsnap::RowSpace();
+        if (!ctx->rowspace) return ctx->fail(FSNAP_E_NOMEM, "out of host memory");
+    }
+    fsnap::RowSpace* rs = ctx->rowspace;
+    const size_t rdoubles = fsnap::trsm_factor_doubles(K16);
+    if (!rs->Rdev.ensure(rdoubles * 8)) return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(row-space workspace) failed");
+    // padded copy of the factor + inverse blocks, as a pass of fsnap_lstsq_rows forms it
+    vec Rpad(rdoubles, 0.0);
+    for (int i = 0; i < K16; ++i) Rpad[(size_t)i * K16 + i] = 1.0;
+    for (int i = 0; i < K; ++i) memcpy(Rpad.data() + (size_t)i * K16 + i, R + (size_t)i * K + i, (size_t)(K - i) * 8);
+    fsnap::trsm_invert_diagonal_blocks(Rpad.data(), K16);
+    hipStream_t st = ctx->stream;
+    FSNAP_HIP(hipMemcpyAsync(rs->Rdev.p, Rpad.data(), rdoubles * 8, hipMemcpyHostToDevice, st), "hipMemcpy(R)");
+    const hipError_t le = first ? fsnap::launch_trsm_family(fam, ctx->dA, ctx->lda, (const double*)ctx->wpack.p, d_Q, K, ctx->m, K,
+                                                            (const double*)rs->Rdev.p, K16, st)
+                                : fsnap::launch_trsm_family(fam, d_Q, K, nullptr, d_Q, K, ctx->m, K, (const double*)rs->Rdev.p, K16, st);
+    // waited for on every path: Rpad is pageable memory that the copy above may still be reading
+    rc = fsnap::wait_stream(ctx, nullptr, "row-space pass");
+    if (le != hipSuccess) return ctx->hipfail(le, "launch fsnap_trsm_rows_k");
+    if (rc == FSNAP_OK && family_run) *family_run = fam;
+    return rc;
+}
+
+int fsnap_qpack_device(fsnap_ctx* ctx, double* d_qpack) {
+    if (!ctx) return FSNAP_E_ARG;
+    if (!d_qpack) return ctx->fail(FSNAP_E_ARG, "fsnap_qpack_device: bad argument");
+    if (!ctx->dA || ctx->m <= 0) return ctx->fail(FSNAP_E_STATE, "no rows: call fsnap_upload_rows/fsnap_bind_rows first");
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    int rc;
+    if ((rc = fsnap::wpack_current(ctx))) return rc;
+    FSNAP_HIP(fsnap::launch_qpack((const double*)ctx->wpack.p, ctx->m, d_qpack, ctx->stream), "launch fsnap_qpack_k");
+    return fsnap::wait_stream(ctx, nullptr, "qpack");
+}
+
 int fsnap_lstsq_rows(fsnap_ctx* ctx, double rcond, int64_t K64, double* beta, int* rank_out, double* info) {
     if (!ctx) return FSNAP_E_ARG;
     if (!beta || K64 <= 0) return ctx->fail(FSNAP_E_ARG, "fsnap_lstsq_rows: bad argument");

@@ -651,10 +651,8 @@ __global__ __launch_bounds__(256) void fsnap_qpack_k(const double* __restrict__ 
 
 namespace fsnap {
 
-hipError_t launch_trsm_rows(const double* src, int64_t lds, const double* wpack, double* Q, int64_t ldq, int64_t m, int K,
-                            const double* R, int K16, hipStream_t st) {
-    const int64_t nb = (m + 63) / 64;
-    if (nb > 0x7FFFFFFF) return hipErrorInvalidValue;
+// The rule: which kernel a pass of m rows and K16 padded columns runs (launch_trsm_rows = the rule + launch_trsm_family).
+int trsm_family(int64_t m, int K16) {
     // K <= 128: kernel 13C (64-column panels, two waves per SIMD) for every pass.  tools/trsm_check, 10^6 rows, round 5 (kernel 13A,
     // one wave per SIMD with the whole 64 x K tile -- gone since -- / 13C, ms): in-place passes K = 128 0.737 / 0.590, 110 0.642 / 0.535,
     // 96 0.517 / 0.383, 64 0.249 / 0.201, 31 0.135 / 0.108; first pass 128 0.765 / 0.709, 110 0.690 / 0.701, 96 0.546 / 0.479
@@ -663,7 +661,19 @@ hipError_t launch_trsm_rows(const double* src, int64_t lds, const double* wpack,
     // Nine blocks (129 ... 144 columns: the ACE width 142 of examples/Ta_PACE_RIDGE) since round 6, from 32 768 rows on: 10^6 x 142
     // 1.31 -> 0.86 ms in place, 1.45 -> 0.92 ms first pass, 10^6 x 144 1.31 -> 0.70 ms (rows of 142 doubles straddle the 128-byte
     // lines); a short system has too few 64-row tiles for one wave each (13 035 x 142: 0.047 against kernel 13B's 0.032 ms)
-    if (K16 <= 128 || (K16 == 144 && m >= 64 * 512)) {
+    if (K16 <= 128 || (K16 == 144 && m >= 64 * 512)) return TRSM_ACC2;
+    // kernel 13B (panels of 128 columns), one wave per SIMD (the row tile in the accumulation registers, everything else
+    // hand-pipelined): 16 rows per wave while that still leaves fewer than two workgroups per CU, 32 rows otherwise (a 64-row
+    // tile -- 256 accumulation registers -- does not leave the 256 VGPRs the rest needs)
+    return m < 64 * 512 ? TRSM_PANEL16 : TRSM_PANEL32;
+}
+
+hipError_t launch_trsm_family(int family, const double* src, int64_t lds, const double* wpack, double* Q, int64_t ldq, int64_t m,
+                              int K, const double* R, int K16, hipStream_t st) {
+    const int64_t nb = (m + 63) / 64;
+    if (nb > 0x7FFFFFFF || K16 < 16 || (K16 & 15) || K > K16 || K + 16 <= K16) return hipErrorInvalidValue;
+    if (family == TRSM_ACC2) {
+        if (K16 > 144) return hipErrorInvalidValue;
         const dim3 grid((unsigned)nb), block(64);
 #define FSNAP_TRSM_ACC2(NBV)                                                                                                 \
     case NBV:                                                                                                                \
@@ -678,26 +688,26 @@ hipError_t launch_trsm_rows(const double* src, int64_t lds, const double* wpack,
 #undef FSNAP_TRSM_ACC2
         return hipGetLastError();
     }
-    // kernel 13B (panels of 128 columns)
-    {
-
-        // one wave per SIMD (the row tile in the accumulation registers, everything else hand-pipelined): 16 rows per wave
-        // while that still leaves fewer than two workgroups per CU, 32 rows otherwise (a 64-row tile -- 256 accumulation registers -- does not leave the 256 VGPRs the rest needs)
-        const int tr = m < 64 * 512 ? 1 : 2;
+    // kernel 13B: never below 129 columns (the rule above)
+    if ((family != TRSM_PANEL16 && family != TRSM_PANEL32) || K16 <= 128) return hipErrorInvalidValue;
 #define FSNAP_TRSM_PANEL(TRV, KGV)                                                                                               \
     {                                                                                                                            \
         const dim3 grid((unsigned)((m + 64 * TRV - 1) / (64 * TRV))), block(256);                                                \
         if (wpack) hipLaunchKernelGGL((fsnap_trsm_panel_k<TRV, KGV, true>), grid, block, 0, st, src, lds, wpack, Q, ldq, m, K, R, K16); \
         else hipLaunchKernelGGL((fsnap_trsm_panel_k<TRV, KGV, false>), grid, block, 0, st, src, lds, wpack, Q, ldq, m, K, R, K16);      \
     }
-        // slab height KG (rows of R staged per barrier): 64 for the 16-row tiles, 16 for the 32-row tiles (measured: 15 213 x
-        // 1 595 1.13 ms with (1, 64), 1.16 with (1, 32); 367 900 x 480 2.58 ms with (2, 16), 2.69 with (2, 32), whose first-pass
-        // variant also spills)
-        if (tr == 1) FSNAP_TRSM_PANEL(1, 64)
-        else FSNAP_TRSM_PANEL(2, 16)
+    // slab height KG (rows of R staged per barrier): 64 for the 16-row tiles, 16 for the 32-row tiles (measured: 15 213 x
+    // 1 595 1.13 ms with (1, 64), 1.16 with (1, 32); 367 900 x 480 2.58 ms with (2, 16), 2.69 with (2, 32), whose first-pass
+    // variant also spills)
+    if (family == TRSM_PANEL16) FSNAP_TRSM_PANEL(1, 64)
+    else FSNAP_TRSM_PANEL(2, 16)
 #undef FSNAP_TRSM_PANEL
-        return hipGetLastError();
-    }
+    return hipGetLastError();
+}
+
+hipError_t launch_trsm_rows(const double* src, int64_t lds, const double* wpack, double* Q, int64_t ldq, int64_t m, int K,
+                            const double* R, int K16, hipStream_t st) {
+    return launch_trsm_family(trsm_family(m, K16), src, lds, wpack, Q, ldq, m, K, R, K16, st);
 }
 
 hipError_t launch_qpack(const double* wpack, int64_t m, double* qpack, hipStream_t st) {

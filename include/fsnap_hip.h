@@ -574,6 +574,20 @@ int fsnap_lstsq_rows(fsnap_ctx* ctx, double rcond, int64_t K, double* beta, int*
 int fsnap_rowspace_factor(int64_t K, const double* G, int first, double tol, double* Rhat, double* Rp, double* info);
 int fsnap_rowspace_solve(int64_t K, const double* Rhat, const double* z, double rcond, double* beta, int* rank, double* info);
 
+/* ONE pass Q <- X R^-1 of that solve on its own (kernels 13B / 13C of fsnap_trsm.hip), for tests and diagnosis: R = K x K
+ * row-major on the host, its upper triangle is read (K = columns of the resident rows); the call pads it to K16 = K rounded
+ * up to 16 with an identity, forms the inverses of its 16 x 16 diagonal blocks, uploads both, runs the pass on the context's
+ * stream and waits -- what a pass of fsnap_lstsq_rows does with the factor of fsnap_rowspace_factor.  first = 1: X =
+ * diag(w_eff) A of the resident rows and weights (rows with w_eff = 0 become +0.0 whatever they hold), written to d_Q
+ * (device, m x K, leading dimension K); first = 0: X = d_Q, in place.  family: 0 = the kernel fsnap_lstsq_rows launches at
+ * (m, K); 1 = kernel 13C (K16 <= 144); 2 = kernel 13B with 16-row tiles, 3 = with 32-row tiles (K16 > 128) -- at row counts
+ * where fsnap_lstsq_rows would pick another one as well.  FSNAP_E_ARG for a family outside its range of widths.
+ * *family_run (may be NULL) = the family that ran: with family = 0, what the rule of fsnap_lstsq_rows picked.
+ * fsnap_qpack_device: the per-row pairs (w_eff != 0 ? 1 : 0, w_eff b) that the statistics of Q are taken with, into d_qpack
+ * (device, 2 m doubles). */
+int fsnap_trsm_pass(fsnap_ctx* ctx, const double* R, int first, int family, double* d_Q, int* family_run);
+int fsnap_qpack_device(fsnap_ctx* ctx, double* d_qpack);
+
 /* The same K x K end for K > 256, where fsnap_lstsq_rows keeps the factors of the passes apart: R = nfac upper triangular
  * K x K factors, R[0] the first pass (R_hat = R[nfac-1] ... R[0] is NOT formed unless a truncation is needed: the product costs
  * K^3 / 3 flops per pass on one host core).  beta = pinv_rcond(R_hat) z: by nfac back substitutions when an upper estimate

@@ -1,5 +1,7 @@
 // tools/trsm_check.hip — stand-alone check + timing of the row-space pass kernels (fsnap_trsm.hip): Q = X R^-1 for a random
-// well-conditioned upper triangular R against a host substitution, error per 16-column block.
+// well-conditioned upper triangular R against a host substitution, error per 16-column block.  A hand-run tool for timing and
+// diagnosis (one shape, a benign R, a fixed 1e-9 threshold); the kernels' accuracy is pinned by tests/test_gpu_trsm.py (every
+// template instance, long-double reference, a-priori bars: tests/trsm_cases.py).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include tools/trsm_check.hip -o tools/trsm_check
 //   tools/trsm_check m K [first=0|1] [reps]
 #include "../fitsnap_amd/csrc/fsnap_trsm.hip"
