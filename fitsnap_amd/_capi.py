@@ -32,6 +32,9 @@ CAND_ERROR_SUMS, CAND_RHS = 0, 1            # fsnap_candidate_rows: what
 UQ_QUAD, UQ_NORM = 0, 1                     # fsnap_row_variance: mode
 SELECT_SUM, SELECT_MAX, SELECT_MEAN = 0, 1, 2   # fsnap_select_begin: objective
 SELECT_OBJECTIVES = {"sum": SELECT_SUM, "max": SELECT_MAX, "mean": SELECT_MEAN}
+ROBUST_HUBER, ROBUST_BISQUARE, ROBUST_CAUCHY = 0, 1, 2   # fsnap_robust_reweight: loss
+ROBUST_LOSSES = {"huber": ROBUST_HUBER, "bisquare": ROBUST_BISQUARE, "cauchy": ROBUST_CAUCHY}
+ROBUST_MAX_CLASSES = 32
 MERR_METHODS = {"iid": MERR_IID, "abc": MERR_ABC, "full": MERR_FULL}
 
 _P_D = POINTER(c_double)
@@ -144,6 +147,13 @@ SIGNATURES = {
                                   c_void_p]),
     "fsnap_joint_retire": (c_int, [c_void_p, c_int64]),
     "fsnap_joint_end": (c_int, [c_void_p]),
+    "fsnap_robust_begin": (c_int, [c_void_p, c_void_p, c_int]),
+    "fsnap_robust_residuals": (c_int, [c_void_p, c_void_p, c_int64]),
+    "fsnap_robust_scale": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "fsnap_robust_reweight": (c_int, [c_void_p, c_int, c_double, c_void_p, c_void_p]),
+    "fsnap_robust_step": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_double, c_void_p, c_void_p]),
+    "fsnap_robust_download": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fsnap_robust_end": (c_int, [c_void_p]),
 }
 
 _lib = None
@@ -958,6 +968,69 @@ class HipContext:
     def joint_end(self):
         """Drop the joint-score session (``fsnap_joint_end``)."""
         self._check(self._lib.fsnap_joint_end(self._h))
+
+    # -- robust IRLS step (fsnap_robust_*) ---------------------------------------------------
+    def robust_begin(self, cat=None, ncat=1):
+        """Start a robust session on the resident rows and their current weights (``fsnap_robust_begin``): ``cat`` is one
+        class id in [0, ncat) per resident row (None = one class)."""
+        if cat is not None:
+            cat = np.ascontiguousarray(cat, dtype=np.int32).reshape(-1)
+            if cat.shape != (self.m,):
+                raise ValueError(f"cat has shape {cat.shape}, expected ({self.m},)")
+        self._check(self._lib.fsnap_robust_begin(self._h, _ptr(cat) if cat is not None and cat.size else None, int(ncat)))
+        self._robust_shape = (self.m, int(ncat))
+
+    def robust_residuals(self, beta):
+        """e_i = w_i (b_i - a_i . beta) with the session's base weights, left on the device (``fsnap_robust_residuals``)."""
+        beta = _f64(beta, "beta").reshape(-1)
+        self._check(self._lib.fsnap_robust_residuals(self._h, _ptr(beta), beta.size))
+
+    def robust_scale(self):
+        """(scale, count) per class: 1.4826 x the exact median of |e| and the participating rows, over all ranks of a
+        communicator (``fsnap_robust_scale``; collective there)."""
+        ncat = getattr(self, "_robust_shape", (0, 1))[1]
+        s, n = np.zeros(ncat), np.zeros(ncat, dtype=np.int64)
+        self._check(self._lib.fsnap_robust_scale(self._h, _ptr(s), _ptr(n)))
+        return s, n
+
+    def _robust_args(self, loss, c, scale):
+        ncat = getattr(self, "_robust_shape", (0, 1))[1]
+        if isinstance(loss, str):
+            if loss not in ROBUST_LOSSES:
+                raise ValueError(f"unknown loss {loss!r}: one of {sorted(ROBUST_LOSSES)}")
+            loss = ROBUST_LOSSES[loss]
+        if scale is not None:
+            scale = _f64(scale, "scale").reshape(-1)
+            if scale.shape != (ncat,):
+                raise ValueError(f"scale has shape {scale.shape}, expected ({ncat},)")
+        return int(loss), float(c), scale, np.zeros((ncat, 6))
+
+    def robust_reweight(self, loss, c, scale=None):
+        """r = sqrt(omega) and w r from the session's residuals; the context's fits read w r from here on
+        (``fsnap_robust_reweight``).  Returns this rank's per-class table (ncat x 6): n, rows with omega < 1, rows with
+        omega = 0, sum omega, sum e^2, sum rho.  ``scale`` None = the scales of the last ``robust_scale``."""
+        loss, c, scale, sums = self._robust_args(loss, c, scale)
+        self._check(self._lib.fsnap_robust_reweight(self._h, loss, c, _ptr(scale), _ptr(sums)))
+        return sums
+
+    def robust_step(self, beta, loss, c, scale=None):
+        """``robust_residuals`` + ``robust_reweight`` in one launch (``fsnap_robust_step``): the same bits, A read once."""
+        beta = _f64(beta, "beta").reshape(-1)
+        loss, c, scale, sums = self._robust_args(loss, c, scale)
+        self._check(self._lib.fsnap_robust_step(self._h, _ptr(beta), beta.size, loss, c, _ptr(scale), _ptr(sums)))
+        return sums
+
+    def robust_download(self, e=True, r=False, wr=False):
+        """Dict of the session's per-row vectors asked for: "e", "r", "wr" (``fsnap_robust_download``)."""
+        m = getattr(self, "_robust_shape", (0, 1))[0]
+        out = {k: np.zeros(m) for k, want in (("e", e), ("r", r), ("wr", wr)) if want}
+        self._check(self._lib.fsnap_robust_download(self._h, _ptr(out.get("e")), _ptr(out.get("r")), _ptr(out.get("wr"))))
+        return out
+
+    def robust_end(self):
+        """End the robust session: the context's weights and mask are those of ``robust_begin`` again
+        (``fsnap_robust_end``)."""
+        self._check(self._lib.fsnap_robust_end(self._h))
 
     def _loco_args(self, M, beta, sorted_rows, cfg_offsets):
         """(M, beta, rows, offsets, K, J, ncfg) of ``loco_rows`` / ``loco_rows_uq``, checked."""

@@ -13,6 +13,8 @@ defaulted here, with the reference's defaults:
   [ARD]    alphabig, alphasmall, lambdabig, lambdasmall, threshold_lambda, directmethod,
            scap=1e-3, scai=1e-3, logcut=0.3                 (solver_sections/ard.py:13-21)
   [LASSO]  alpha=1.0E-8, max_iter=2000                      (solver_sections/lasso.py:13-14)
+  [ROBUST] loss=huber, tune (per loss), alpha=1.0E-8, scale_by=row_type, scale_iters=0, max_iter=50, tol=1.0E-8
+                                                            (solvers/robust.py; no counterpart in the reference)
   [EXTRAS] apply_transpose, multinode_testing, only_test, dump_*   (extras.py:19-45)
   [CALCULATOR] calculator, energy, force, stress, per_atom_energy, linear
                                                             (calculator_sections/calculator.py:17-32)
@@ -207,6 +209,19 @@ class Config:
                 not_used("LASSO")
             self.sections["LASSO"] = SimpleNamespace(name="LASSO", alpha=_get(ld, "alpha", "1.0E-8", "float"),
                                                      max_iter=_get(ld, "max_iter", "2000", "int"))
+
+        if "ROBUST" in raw or solver.upper() == "ROBUST":
+            rb = raw.get("ROBUST", {})
+            _check_keys("ROBUST", rb, ["loss", "tune", "alpha", "scale_by", "scale_iters", "max_iter", "tol"])
+            if solver.upper() != "ROBUST":
+                not_used("ROBUST")
+            loss = _get(rb, "loss", "huber", "str").strip().lower()
+            tune = _get(rb, "tune", "", "str").strip()
+            self.sections["ROBUST"] = SimpleNamespace(
+                name="ROBUST", loss=loss, tune=float(tune) if tune else None,      # None: the loss's own default
+                alpha=_get(rb, "alpha", "1.0E-8", "float"), scale_by=_get(rb, "scale_by", "row_type", "str").strip().lower(),
+                scale_iters=_get(rb, "scale_iters", "0", "int"), max_iter=_get(rb, "max_iter", "50", "int"),
+                tol=_get(rb, "tol", "1.0E-8", "float"))
 
         ex = raw.get("EXTRAS", {})
         _check_keys("EXTRAS", ex, ["multinode_testing", "apply_transpose", "only_test", "dump_descriptors", "dump_truth",

@@ -395,6 +395,18 @@ void cand_forget(fsnap_ctx* ctx) {
     ctx->cand_stats_K = 0;
 }
 
+// a robust session (fsnap_robust_*) belongs to the rows AND the weights it was begun with: new rows or new weights end it
+// without restoring anything.  new_rows: the session's w r are not weights of the new rows -- none until the caller sets some
+void robust_forget(fsnap_ctx* ctx, bool new_rows) {
+    if (new_rows && ctx->rob_active && ctx->rob_pointed && ctx->dw == (const double*)ctx->rob_wr.p) {
+        ctx->dw = nullptr;
+        ctx->dmask = nullptr;
+        ctx->wpack_valid = false;
+    }
+    ctx->rob_active = ctx->rob_pointed = false;
+    if (new_rows) ctx->rob_have_e = ctx->rob_have_r = false;      // (new weights: e, r, w r of the last pass stay downloadable)
+}
+
 int check_rows(fsnap_ctx* ctx) {
     if (!ctx->dA || !ctx->db || ctx->m <= 0) return ctx->fail(FSNAP_E_STATE, "no rows: call fsnap_upload_rows/fsnap_bind_rows first");
     return FSNAP_OK;
@@ -978,6 +990,7 @@ int fsnap_upload_rows(fsnap_ctx* ctx, const double* A, int64_t m, int64_t K, int
     ctx->K = K;
     ctx->lda = K;
     cand_forget(ctx);
+    robust_forget(ctx, true);
     return FSNAP_OK;
 }
 
@@ -991,6 +1004,7 @@ int fsnap_drop_rows(fsnap_ctx* ctx) {
     ctx->dmask = nullptr;
     ctx->m = 0;
     cand_forget(ctx);
+    robust_forget(ctx, true);
     ctx->ntrain_resident = -1;
     ctx->wpack_valid = false;
     ctx->mirror_of = nullptr;
@@ -1018,6 +1032,7 @@ int fsnap_bind_rows(fsnap_ctx* ctx, const double* dA, int64_t m, int64_t K, int6
     ctx->K = K;
     ctx->lda = lda;
     cand_forget(ctx);
+    robust_forget(ctx, true);
     return FSNAP_OK;
 }
 
@@ -1043,6 +1058,7 @@ int fsnap_rows_alloc(fsnap_ctx* ctx, int64_t m, int64_t K) {
     ctx->K = K;
     ctx->lda = K;
     cand_forget(ctx);
+    robust_forget(ctx, true);
     return FSNAP_OK;
 }
 
@@ -1129,6 +1145,7 @@ int fsnap_assemble(fsnap_ctx* ctx, const double* raw, int64_t raw_rows, int64_t 
     hipStream_t st = ctx->stream;
     ctx->wpack_valid = false;      // the kernel below writes b and w of these rows
     cand_forget(ctx);
+    robust_forget(ctx, true);
     FSNAP_HIP(fsnap::launch_assemble(pd.raw, raw_ld, nrows, pd.src_row, pd.kind, pd.frac, pd.d, pd.truth, pd.weight,
                                      pd.fractions, pd.blank2J, ntypes, ncoeff, offcol,
                                      (double*)ctx->ownA.p + row0 * ctx->lda, ctx->lda, (double*)ctx->ownb.p + row0,
@@ -1225,6 +1242,7 @@ int fsnap_set_weights(fsnap_ctx* ctx, const double* w, const uint8_t* mask) {
     if ((rc = staged_h2d(ctx, ctx->ownw.p, w, m * 8))) return rc;
     ctx->dw = (const double*)ctx->ownw.p;
     ctx->wpack_valid = false;
+    robust_forget(ctx, false);
     if (mask) {
         if (!ctx->ownmask.ensure(m)) return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(mask) failed");
         if ((rc = staged_h2d(ctx, ctx->ownmask.p, mask, m))) return rc;
@@ -1261,6 +1279,7 @@ int fsnap_set_weights_train(fsnap_ctx* ctx, const double* w_train, int64_t ntrai
     ctx->dw = (const double*)ctx->ownw.p;
     ctx->dmask = (const unsigned char*)ctx->ownmask.p;
     ctx->wpack_valid = false;
+    robust_forget(ctx, false);
     return FSNAP_OK;
 }
 
@@ -1272,6 +1291,7 @@ int fsnap_bind_weights(fsnap_ctx* ctx, const double* dw, const uint8_t* dmask) {
     ctx->dw = dw;
     ctx->dmask = dmask;
     ctx->wpack_valid = false;
+    robust_forget(ctx, false);
     ctx->ntrain_resident = -1;
     return FSNAP_OK;
 }
@@ -3222,5 +3242,215 @@ int fsnap_joint_retire(fsnap_ctx* ctx, int64_t unit) {
 int fsnap_joint_end(fsnap_ctx* ctx) {
     if (!ctx) return FSNAP_E_ARG;
     ctx->joint_active = false;
+    return FSNAP_OK;
+}
+
+// ---- robust M-estimator fits by IRLS: the step between two fits (kernels R0 - R3 of fsnap_robust.hip) --------------------
+
+namespace {
+
+int robust_session(fsnap_ctx* ctx, const char* who) {
+    if (!ctx->rob_active)
+        return ctx->fail(FSNAP_E_STATE, "%s: no robust session (fsnap_robust_begin; new rows or new weights end one)", who);
+    return FSNAP_OK;
+}
+
+// r, w r and the per-class sums from the session's residuals (rows == false) or from the rows themselves (one launch)
+int robust_weights(fsnap_ctx* ctx, const char* who, bool rows, int loss, double c, const double* scale, double* sums) {
+    if (loss != FSNAP_ROBUST_HUBER && loss != FSNAP_ROBUST_BISQUARE && loss != FSNAP_ROBUST_CAUCHY)
+        return ctx->fail(FSNAP_E_ARG, "%s: unknown loss %d", who, loss);
+    if (!(c > 0.0) || !std::isfinite(c)) return ctx->fail(FSNAP_E_ARG, "%s: the tuning constant must be positive", who);
+    if (!scale && !ctx->rob_have_scale) return ctx->fail(FSNAP_E_STATE, "%s: no scales yet (fsnap_robust_scale, or pass them)", who);
+    if (!rows && !ctx->rob_have_e && ctx->rob_m > 0) return ctx->fail(FSNAP_E_STATE, "%s: no residuals yet (fsnap_robust_residuals)", who);
+    const int ncat = ctx->rob_ncat;
+    const int64_t m = ctx->rob_m;
+    if (sums) std::memset(sums, 0, (size_t)ncat * 6 * 8);
+    double* dscale = fsnap::robust_scale_ptr(ctx->rob_state.p, ncat);
+    if (scale) {
+        for (int g = 0; g < ncat; ++g)
+            if (!(scale[g] >= 0.0)) return ctx->fail(FSNAP_E_ARG, "%s: scale[%d] is negative or NaN", who, g);
+        FSNAP_HIP(hipMemcpyAsync(dscale, scale, (size_t)ncat * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(scale)");
+        ctx->rob_have_scale = true;
+    }
+    if (m > 0) {
+        const int nb = fsnap::robust_num_blocks(m, (int)ctx->K);
+        if (!ctx->rob_part.ensure((size_t)nb * ncat * 6 * 8) || !ctx->rob_sums.ensure((size_t)ncat * 6 * 8))
+            return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(robust partials) failed");
+        FSNAP_HIP(hipEventRecord(ctx->ev[7], ctx->stream), "hipEventRecord");       // (the row pass's slot of fsnap_timing)
+        FSNAP_HIP(fsnap::launch_robust_rows(ctx->dA, ctx->lda, (const double*)ctx->beta.p, m, (int)ctx->K, ctx->db, ctx->rob_dw,
+                                            (const int*)ctx->rob_pcat.p, rows ? nullptr : (const double*)ctx->rob_e.p,
+                                            (double*)ctx->rob_e.p, true, loss, c, dscale, (double*)ctx->rob_r.p,
+                                            (double*)ctx->rob_wr.p, (double*)ctx->rob_part.p, (double*)ctx->rob_sums.p, ncat,
+                                            ctx->stream),
+                  "launch fsnap_robust_rows_k");
+        FSNAP_HIP(hipEventRecord(ctx->ev[8], ctx->stream), "hipEventRecord");
+        ctx->t_predict = true;
+        if (rows) ctx->rob_have_e = true;
+        if (sums) FSNAP_HIP(hipMemcpyAsync(sums, ctx->rob_sums.p, (size_t)ncat * 6 * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(sums)");
+        // from here on the context's fits read w r
+        ctx->dw = (const double*)ctx->rob_wr.p;
+        ctx->wpack_valid = false;
+        ctx->rob_pointed = true;
+        ctx->rob_have_r = true;
+    }
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    return FSNAP_OK;
+}
+
+int robust_check_beta(fsnap_ctx* ctx, const char* who, const double* beta, int64_t K) {
+    if (!beta) return ctx->fail(FSNAP_E_ARG, "%s: beta is NULL", who);
+    if (ctx->rob_m > 0 && K != ctx->K)
+        return ctx->fail(FSNAP_E_ARG, "%s: K = %lld, the resident rows have %lld columns", who, (long long)K, (long long)ctx->K);
+    if (K < 1) return ctx->fail(FSNAP_E_ARG, "%s: K = %lld", who, (long long)K);
+    if (ctx->rob_m > 0) {
+        if (!ctx->beta.ensure((size_t)K * 8)) return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(beta) failed");
+        FSNAP_HIP(hipMemcpyAsync(ctx->beta.p, beta, (size_t)K * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(beta)");
+    }
+    return FSNAP_OK;
+}
+
+}  // namespace
+
+int fsnap_robust_end(fsnap_ctx* ctx) {
+    if (!ctx) return FSNAP_E_ARG;
+    if (ctx->rob_active) {
+        ctx->dw = ctx->rob_dw;
+        ctx->dmask = ctx->rob_dmask;
+        // the packed pairs in wpack are those of the base weights only if no fit of the session has rewritten them
+        ctx->wpack_valid = ctx->rob_pointed ? false : ctx->rob_wpack_valid;
+    }
+    ctx->rob_active = false;
+    ctx->rob_pointed = false;
+    return FSNAP_OK;
+}
+
+int fsnap_robust_begin(fsnap_ctx* ctx, const int32_t* cat, int ncat) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_robust_begin";
+    (void)fsnap_robust_end(ctx);
+    if (ncat < 1 || ncat > FSNAP_ROBUST_MAX_CLASSES)
+        return ctx->fail(FSNAP_E_ARG, "%s: ncat = %d, the kernels hold 1 ... %d classes", who, ncat, FSNAP_ROBUST_MAX_CLASSES);
+    const bool have_rows = ctx->dA && ctx->db && ctx->m > 0;
+    if (!have_rows && !ctx->comm) return check_rows(ctx);
+    const int64_t m = have_rows ? ctx->m : 0;
+    int rc;
+    if (m > 0 && (rc = check_weights(ctx))) return rc;
+    for (int64_t i = 0; cat && i < m; ++i)
+        if (cat[i] < 0 || cat[i] >= ncat) return ctx->fail(FSNAP_E_ARG, "%s: class %d of row %lld is outside [0, %d)", who, cat[i], (long long)i, ncat);
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    const size_t mm = (size_t)std::max<int64_t>(m, 1);
+    if (!ctx->rob_pcat.ensure(mm * 4) || !ctx->rob_e.ensure(mm * 8) || !ctx->rob_r.ensure(mm * 8) || !ctx->rob_wr.ensure(mm * 8) ||
+        !ctx->rob_state.ensure(fsnap::robust_state_bytes(ncat)))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(robust session) failed");
+    if (m > 0) {
+        // the class ids travel through the session's residual vector (m x 4 bytes fit in its m x 8) and are folded with the
+        // base weights and the mask into the participating class of every row
+        const int* dcat = nullptr;
+        if (cat) {
+            FSNAP_HIP(hipMemcpyAsync(ctx->rob_e.p, cat, (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(classes)");
+            dcat = (const int*)ctx->rob_e.p;
+        }
+        FSNAP_HIP(fsnap::launch_robust_pcat(ctx->dw, ctx->dmask, dcat, m, (int*)ctx->rob_pcat.p, ctx->stream), "launch fsnap_robust_pcat_k");
+    }
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    ctx->rob_dw = ctx->dw;
+    ctx->rob_dmask = ctx->dmask;
+    ctx->rob_wpack_valid = ctx->wpack_valid;
+    ctx->rob_ncat = ncat;
+    ctx->rob_m = m;
+    ctx->rob_have_e = ctx->rob_have_r = ctx->rob_have_scale = ctx->rob_pointed = false;
+    ctx->rob_active = true;
+    return FSNAP_OK;
+}
+
+int fsnap_robust_residuals(fsnap_ctx* ctx, const double* beta, int64_t K) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_robust_residuals";
+    int rc = robust_session(ctx, who);
+    if (rc) return rc;
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    if ((rc = robust_check_beta(ctx, who, beta, K))) return rc;
+    if (ctx->rob_m > 0) {
+        FSNAP_HIP(hipEventRecord(ctx->ev[7], ctx->stream), "hipEventRecord");       // (the row pass's slot of fsnap_timing)
+        FSNAP_HIP(fsnap::launch_robust_rows(ctx->dA, ctx->lda, (const double*)ctx->beta.p, ctx->rob_m, (int)K, ctx->db, ctx->rob_dw,
+                                            (const int*)ctx->rob_pcat.p, nullptr, (double*)ctx->rob_e.p, false, 0, 1.0, nullptr,
+                                            nullptr, nullptr, nullptr, nullptr, ctx->rob_ncat, ctx->stream),
+                  "launch fsnap_robust_rows_k");
+        FSNAP_HIP(hipEventRecord(ctx->ev[8], ctx->stream), "hipEventRecord");
+        ctx->t_predict = true;
+        FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");       // the caller's beta may be reused
+    }
+    ctx->rob_have_e = true;
+    return FSNAP_OK;
+}
+
+int fsnap_robust_scale(fsnap_ctx* ctx, double* scale, int64_t* count) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_robust_scale";
+    int rc = robust_session(ctx, who);
+    if (rc) return rc;
+    if (!ctx->rob_have_e && ctx->rob_m > 0) return ctx->fail(FSNAP_E_STATE, "%s: no residuals yet (fsnap_robust_residuals)", who);
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    const int ncat = ctx->rob_ncat;
+    void* st = ctx->rob_state.p;
+    FSNAP_HIP(hipMemsetAsync(st, 0, fsnap::robust_state_bytes(ncat), ctx->stream), "hipMemsetAsync(robust state)");
+    for (int pass = 0; pass < 8; ++pass) {
+        FSNAP_HIP(fsnap::launch_robust_hist((const double*)ctx->rob_e.p, (const int*)ctx->rob_pcat.p, ctx->rob_m, pass, ncat, st,
+                                            ctx->stream),
+                  "launch fsnap_robust_hist_k");
+        if (ctx->comm) {
+            FSNAP_HIP(fsnap::launch_robust_table_to_double(st, ncat, ctx->stream), "launch fsnap_robust_table_to_double_k");
+            if ((rc = fsnap_allreduce_device(ctx, fsnap::robust_table_doubles(st, ncat), (int64_t)ncat * 512))) return rc;
+        }
+        FSNAP_HIP(fsnap::launch_robust_choose(st, pass, ncat, ctx->comm != nullptr, ctx->stream), "launch fsnap_robust_choose_k");
+    }
+    std::vector<double> hs((size_t)ncat);
+    std::vector<long long> hn((size_t)ncat);
+    FSNAP_HIP(hipMemcpyAsync(hs.data(), fsnap::robust_scale_ptr(st, ncat), (size_t)ncat * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(scale)");
+    FSNAP_HIP(hipMemcpyAsync(hn.data(), fsnap::robust_count_ptr(st, ncat), (size_t)ncat * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(count)");
+    if ((rc = fsnap::wait_stream(ctx, nullptr, "robust scale"))) return rc;
+    for (int g = 0; g < ncat; ++g) {
+        if (scale) scale[g] = hs[(size_t)g];
+        if (count) count[g] = (int64_t)hn[(size_t)g];
+    }
+    ctx->rob_have_scale = true;
+    return FSNAP_OK;
+}
+
+int fsnap_robust_reweight(fsnap_ctx* ctx, int loss, double c, const double* scale, double* sums) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_robust_reweight";
+    int rc = robust_session(ctx, who);
+    if (rc) return rc;
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    return robust_weights(ctx, who, false, loss, c, scale, sums);
+}
+
+int fsnap_robust_step(fsnap_ctx* ctx, const double* beta, int64_t K, int loss, double c, const double* scale, double* sums) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_robust_step";
+    int rc = robust_session(ctx, who);
+    if (rc) return rc;
+    if (loss != FSNAP_ROBUST_HUBER && loss != FSNAP_ROBUST_BISQUARE && loss != FSNAP_ROBUST_CAUCHY)
+        return ctx->fail(FSNAP_E_ARG, "%s: unknown loss %d", who, loss);
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    if ((rc = robust_check_beta(ctx, who, beta, K))) return rc;
+    return robust_weights(ctx, who, true, loss, c, scale, sums);
+}
+
+int fsnap_robust_download(fsnap_ctx* ctx, double* e, double* r, double* wr) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_robust_download";
+    // the vectors outlive fsnap_robust_end (diagnostics are fetched after the loop), not new rows or new weights
+    if (!ctx->rob_active && !ctx->rob_have_e && !ctx->rob_have_r) return robust_session(ctx, who);
+    const size_t m = (size_t)ctx->rob_m;
+    if (m == 0) return FSNAP_OK;
+    if (e && !ctx->rob_have_e) return ctx->fail(FSNAP_E_STATE, "%s: no residuals yet", who);
+    if ((r || wr) && !ctx->rob_have_r) return ctx->fail(FSNAP_E_STATE, "%s: no weights yet (fsnap_robust_reweight)", who);
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    if (e) FSNAP_HIP(hipMemcpyAsync(e, ctx->rob_e.p, m * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(e)");
+    if (r) FSNAP_HIP(hipMemcpyAsync(r, ctx->rob_r.p, m * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(r)");
+    if (wr) FSNAP_HIP(hipMemcpyAsync(wr, ctx->rob_wr.p, m * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(wr)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
     return FSNAP_OK;
 }

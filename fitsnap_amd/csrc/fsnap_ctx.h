@@ -160,6 +160,17 @@ struct fsnap_ctx {
     std::vector<unsigned char> joint_halive;
     bool joint_active = false;
     int64_t joint_m = 0, joint_npos = 0, joint_nunits = 0;
+    // fsnap_robust_*: the session's participating class per row, residuals e, r = sqrt(omega), the weights w r the fits read
+    // while the session lasts, the selection state (prefixes, ranks, counts, scales, digit tables), per-workgroup partials and
+    // sums; rob_dw / rob_dmask / rob_wpack_valid are the context's weights as they were at begin (put back by end).
+    // rob_active is cleared by everything that changes the rows (cand_forget).
+    DevBuf rob_pcat, rob_e, rob_r, rob_wr, rob_state, rob_part, rob_sums;
+    bool rob_active = false, rob_wpack_valid = false, rob_pointed = false, rob_have_e = false, rob_have_scale = false;
+    bool rob_have_r = false;                      // r / w r of the last session can still be downloaded (also after its end)
+    const double* rob_dw = nullptr;
+    const unsigned char* rob_dmask = nullptr;
+    int rob_ncat = 0;
+    int64_t rob_m = 0;
     double* pinned = nullptr;                     // page-locked host staging of the packed statistics: plain (coarse-grained)
                                                   // pinned memory, the target of DMA copies only -- copies into COHERENT
                                                   // host memory were bimodal (2 MB in 0.05 or in 8 ms)

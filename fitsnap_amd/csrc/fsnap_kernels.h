@@ -304,6 +304,33 @@ hipError_t launch_joint_units(int D, int nblocks, const double* ZP, int Wp, int 
                               const int64_t* off, const int* ulist, int ncl, double* Sg, int dmax, double* Yg, double* out,
                               double* info, hipStream_t st);
 
+// Robust M-estimator fits by IRLS (fsnap_robust.hip).  pcat[m]: class of every participating row (training row with w > 0),
+// -1 for the others (kernel R0).  Kernel R1 / R3 (launch_robust_rows): e_in == nullptr: e_out[i] = w_i (b_i - a_i . beta) from
+// one pass over A; e_in != nullptr: A, beta, b are not read.  do_weights: r_out[i] = sqrt(omega), wr_out[i] = w_i r_i (rows that
+// do not take part: r = 1, w r = w) and sums[ncat][6] = (n, rows with r < 1, rows with r = 0, sum omega, sum e^2, sum rho) per
+// class, from scale[ncat] on the device; partial: robust_num_blocks(m, K) x ncat x 6 doubles of scratch.  A launch with the
+// rows and one without them give the same bits when m and K agree.  1 <= ncat <= ROBUST_MAX_CLASSES.
+constexpr int ROBUST_HUBER = 0, ROBUST_BISQUARE = 1, ROBUST_CAUCHY = 2;
+constexpr int ROBUST_MAX_CLASSES = 32;
+int robust_num_blocks(int64_t m, int K);
+hipError_t launch_robust_pcat(const double* w, const unsigned char* mask, const int* cat, int64_t m, int* pcat, hipStream_t st);
+hipError_t launch_robust_rows(const double* A, int64_t lda, const double* beta, int64_t m, int K, const double* b, const double* w,
+                              const int* pcat, const double* e_in, double* e_out, bool do_weights, int loss, double c,
+                              const double* scale, double* r_out, double* wr_out, double* partial, double* sums, int ncat,
+                              hipStream_t st);
+// Kernel R2: exact per-class medians of |e| by radix selection over the 8 bytes of the bit pattern.  state:
+// robust_state_bytes(ncat) bytes on the device, zeroed before pass 0.  Per pass: launch_robust_hist (m = 0: nothing), then --
+// in a communicator -- launch_robust_table_to_double, an all-reduce of robust_table_doubles() (512 ncat doubles), and
+// launch_robust_choose (summed = the doubles hold the counts).  After pass 7 robust_scale_ptr() holds 1.4826 x median per class
+// (0 for an empty class) and robust_count_ptr() the rows per class.
+size_t robust_state_bytes(int ncat);
+hipError_t launch_robust_hist(const double* e, const int* pcat, int64_t m, int pass, int ncat, void* state, hipStream_t st);
+hipError_t launch_robust_table_to_double(void* state, int ncat, hipStream_t st);
+hipError_t launch_robust_choose(void* state, int pass, int ncat, bool summed, hipStream_t st);
+double* robust_table_doubles(void* state, int ncat);
+double* robust_scale_ptr(void* state, int ncat);
+long long* robust_count_ptr(void* state, int ncat);
+
 // Row-space solve (fsnap_trsm.hip).  Q <- X R^-1 by blocked substitution over the columns, one wave per 64 rows:
 // first pass X = diag(w_eff) A (src = A, leading dimension lds, per-row pairs wpack = (w_eff, w_eff b); rows with
 // w_eff = 0 become zero rows), later passes X = Q in place (src = Q, wpack = nullptr).  R: device, K16 x K16 row-major

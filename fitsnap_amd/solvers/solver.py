@@ -1245,3 +1245,30 @@ class Solver:
         ``cv_se`` of it.  Neither the fit nor the config is changed.  Raises ValueError for other solvers, for
         ``apply_transpose``, for an empty grid and for unknown grid keys."""
         return ard_path.ard_path(self, grid, folds, by, fs_dict, b, w, tol, max_iter, method, table, seed)
+
+    # ------------------------------------------------------------------------------
+    # robust M-estimator fits by IRLS (solvers/robust.py, csrc/fsnap_robust.hip)
+    # ------------------------------------------------------------------------------
+    def robust_fit(self, loss="huber", tune=None, alpha=None, by="Row_Type", scale=None, scale_iters=0, max_iter=50, tol=1e-8,
+                   start=None, a=None, b=None, w=None, fs_dict=None, trainall=False):
+        """A fit that a few percent of wrong rows do not pull: an M-estimator (``loss``: "huber", "bisquare" or "cauchy";
+        ``tune``: its constant, None = 1.345 / 4.685 / 2.385) by iteratively re-weighted least squares with a robust scale
+        (1.4826 x the median of |w_i (b_i - a_i . beta)|) per class of rows, every iteration on the GPU: one pass over the
+        resident rows for the residuals, an exact per-class median by radix selection, the weights w_i r_i, and the
+        solver's own statistics -> solve path (ridge term ``alpha``, None = ``[ROBUST] alpha`` or 1e-8) reading them.  No
+        m-length vector crosses the bus.  ``by``: what shares a scale -- "Row_Type" (default: energy, force and stress rows
+        do not share a residual scale even after weighting; one global scale would reject a whole row type),
+        "Groups+Row_Type", None (one scale) or one integer class id per row; at most 32 classes.  ``scale``: fixed scales
+        (one per class, in sorted key order) instead of the MAD; ``scale_iters``: re-estimate the scales in the first
+        iterations only (0 = in every one).  Stops when max |beta_new - beta| <= ``tol`` max |beta_new| or after ``max_iter``
+        fits; ``start``: beta_0 instead of the ordinary weighted fit.  Rows, truths, weights and the training mask as
+        ``perform_fit`` takes them (``a, b, w, fs_dict, trainall``); participating rows are the training rows with w > 0.
+        Collective on the native transports (every iteration's fit is ``fsnap_fit_dist``, the medians are those of all
+        ranks' rows, bit for bit on every rank); NotImplementedError under a ``torch.distributed`` group.  The context's
+        weights are the caller's again afterwards, also when an argument or the device raises.  Returns
+        ``robust.RobustResult`` (``fit``, ``iterations``, ``converged``, per-iteration ``scales`` and per-class ``tables``,
+        ``omega()``, ``table(by="Configs" | "Groups")``: the suspect units) and leaves ``self.fit`` on rank 0."""
+        from . import robust
+
+        return robust.robust_fit(self, loss, tune, alpha, by, scale, scale_iters, max_iter, tol, start, a, b, w, fs_dict,
+                                 trainall)

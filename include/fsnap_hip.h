@@ -479,6 +479,45 @@ int fsnap_joint_score(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, int
 int fsnap_joint_retire(fsnap_ctx* ctx, int64_t unit);
 int fsnap_joint_end(fsnap_ctx* ctx);
 
+/* The step between two fits of a robust M-estimator by iteratively re-weighted least squares (kernels R0 - R3 of
+ * csrc/fsnap_robust.hip; the loop is solvers/robust.py).  Participating rows are the training rows with w_i > 0 of the
+ * weights and mask the context holds at begin (the BASE weights); no other row reaches a sum, a median or a count.
+ * A session, like fsnap_select_*:
+ *   fsnap_robust_begin      cat (host, m int32 in [0, ncat), NULL = one class) is uploaded once, the session's vectors
+ *                           (e, r, w r: m doubles each) are allocated and the context's weights and mask remembered.
+ *                           1 <= ncat <= FSNAP_ROBUST_MAX_CLASSES.  In a communicator a rank without rows opens a session
+ *                           of zero rows; without one, no rows is FSNAP_E_STATE.  A running session is ended first.
+ *   fsnap_robust_residuals  e_i = w_i (b_i - a_i . beta) with the base weights, one pass over A; stays on the device.
+ *   fsnap_robust_scale      s_g = 1.4826 median{|e_i| : class g} by radix selection on the bit pattern of |e| (eight digit
+ *                           passes, no host synchronisation between them; both middle order statistics, (lo + hi) * 0.5 for
+ *                           an even count; 0 for an empty class).  Collective in a communicator: the digit tables are summed
+ *                           over the ranks, every rank gets the same bits.  scale, count (host, ncat; either may be NULL).
+ *   fsnap_robust_reweight   r_i = sqrt(omega(e_i / s_g)) for loss = FSNAP_ROBUST_HUBER / _BISQUARE / _CAUCHY with tuning
+ *                           constant c > 0, from scale (host, ncat; NULL = the scales of the last fsnap_robust_scale);
+ *                           s_g = 0: r = 1.  sums (host, ncat x 6, may be NULL) = n, rows with omega < 1, rows with
+ *                           omega = 0, sum omega, sum e^2, sum rho per class, of THIS rank's rows.  From then on the
+ *                           context's fits (fsnap_fit_resident, fsnap_fit_dist, fsnap_normal_eq*) read w_i r_i.
+ *   fsnap_robust_step       residuals + reweight in one launch: A is read once and no m-vector a second time; the bits of
+ *                           the two separate calls.  Needs scales (argument, or an earlier fsnap_robust_scale).
+ *   fsnap_robust_download   e, r, wr (host, m doubles; each may be NULL): diagnostics, on demand; also after
+ *                           fsnap_robust_end, until the rows change.
+ *   fsnap_robust_end        puts the context's weights, mask and packed-weight state back exactly as they were at begin.
+ * New rows or new weights (fsnap_upload_rows, fsnap_bind_rows, fsnap_set_weights*, fsnap_bind_weights ...) end a session
+ * without restoring anything.  FSNAP_E_ARG: K is not the rows' width, unknown loss, c <= 0, ncat or a class id out of range;
+ * FSNAP_E_STATE: no rows, no weights, no session, no residuals or no scales yet.  Every sum is folded in a fixed order and
+ * the selection uses integer atomics only: bit-identical run to run.  Host in and out, synchronous. */
+#define FSNAP_ROBUST_HUBER 0
+#define FSNAP_ROBUST_BISQUARE 1
+#define FSNAP_ROBUST_CAUCHY 2
+#define FSNAP_ROBUST_MAX_CLASSES 32
+int fsnap_robust_begin(fsnap_ctx* ctx, const int32_t* cat, int ncat);
+int fsnap_robust_residuals(fsnap_ctx* ctx, const double* beta, int64_t K);
+int fsnap_robust_scale(fsnap_ctx* ctx, double* scale, int64_t* count);
+int fsnap_robust_reweight(fsnap_ctx* ctx, int loss, double c, const double* scale, double* sums);
+int fsnap_robust_step(fsnap_ctx* ctx, const double* beta, int64_t K, int loss, double c, const double* scale, double* sums);
+int fsnap_robust_download(fsnap_ctx* ctx, double* e, double* r, double* wr);
+int fsnap_robust_end(fsnap_ctx* ctx);
+
 /* ---- K x K solve (host side, no context needed) ----------------------------------- */
 
 /* Solve the K x K system given the statistics.  `kind` is one of FSNAP_SOLVE_*;
