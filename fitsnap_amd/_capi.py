@@ -32,6 +32,7 @@ CAND_ERROR_SUMS, CAND_RHS = 0, 1            # fsnap_candidate_rows: what
 UQ_QUAD, UQ_NORM = 0, 1                     # fsnap_row_variance: mode
 SELECT_SUM, SELECT_MAX, SELECT_MEAN = 0, 1, 2   # fsnap_select_begin: objective
 SELECT_OBJECTIVES = {"sum": SELECT_SUM, "max": SELECT_MAX, "mean": SELECT_MEAN}
+INFL_SCORES, INFL_FULL = 0, 1                   # fsnap_influence_rows: mode
 ROBUST_HUBER, ROBUST_BISQUARE, ROBUST_CAUCHY = 0, 1, 2   # fsnap_robust_reweight: loss
 ROBUST_LOSSES = {"huber": ROBUST_HUBER, "bisquare": ROBUST_BISQUARE, "cauchy": ROBUST_CAUCHY}
 ROBUST_MAX_CLASSES = 32
@@ -130,6 +131,8 @@ SIGNATURES = {
                                 c_void_p]),
     "fsnap_loco_rows_uq": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                    c_void_p, c_void_p]),
+    "fsnap_influence_rows": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fsnap_ridge_path": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
                                  c_int64, c_void_p, c_void_p, c_void_p]),
     "fsnap_lasso_path": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_double, c_void_p,
@@ -1075,6 +1078,30 @@ class HipContext:
         self._check(self._lib.fsnap_loco_rows_uq(self._h, K, J, _ptr(M), _ptr(beta), _ptr(rows) if rows.size else None,
                                                  _ptr(off), ncfg, _ptr(pred), _ptr(lev), _ptr(info)))
         return pred, lev, info
+
+    def influence_rows(self, M, beta, sorted_rows, cfg_offsets, mode=INFL_FULL, want_pred=True, want_vectors=True,
+                       want_sums=True):
+        """Per-configuration influence vectors and the outer-product sums of the cluster-robust covariances
+        (``fsnap_influence_rows``); arguments as ``loco_rows``.  ``mode``: ``INFL_FULL`` (s_c, v_c, W_s, W_v and the
+        predictions) or ``INFL_SCORES`` (s_c and W_s alone: no factorisation).  Returns a dict: "info" (ncfg x 4, as
+        ``loco_rows``; SCORES: d_c, inf, 1, n space), "unit" (ncfg x 3: |v_c|^2, |s_c|^2, s_c . v_c; first and third NaN when
+        c is not identifiable or in SCORES mode), "S" (ncfg x J; None without ``want_vectors``), "Ws" (J x J; None without
+        ``want_sums``) and, in FULL mode, "pred" (m, ``loco_rows``' bits; None without ``want_pred``), "V" (ncfg x J, zeros
+        where c is not identifiable) and "Wv"."""
+        M, beta, rows, off, K, J, ncfg = self._loco_args(M, beta, sorted_rows, cfg_offsets)
+        if mode not in (INFL_SCORES, INFL_FULL):
+            raise ValueError(f"mode {mode!r} (INFL_SCORES, INFL_FULL)")
+        full = mode == INFL_FULL
+        # without units or rows the entry point writes the sums only: the rest keeps what an empty layout means
+        out = {"pred": np.full(self.m, np.nan) if full and want_pred else None,
+               "info": np.tile(np.array([0.0, np.inf, 1.0, 1.0]), (ncfg, 1)),
+               "unit": np.zeros((ncfg, 3)), "S": np.zeros((ncfg, J)) if want_vectors else None,
+               "V": np.zeros((ncfg, J)) if full and want_vectors else None, "Ws": np.empty((J, J)) if want_sums else None,
+               "Wv": np.empty((J, J)) if full and want_sums else None}
+        self._check(self._lib.fsnap_influence_rows(self._h, mode, K, J, _ptr(M), _ptr(beta), _ptr(rows) if rows.size else None,
+                                                   _ptr(off), ncfg, *(_ptr(out[k]) if out[k] is not None else None
+                                                                      for k in ("pred", "info", "unit", "S", "V", "Ws", "Wv"))))
+        return out
 
     def ridge_path(self, G, c, alphas, sorted_rows, unit_offsets, row_class, nclass, want_preds=False):
         """Leave-one-unit-out refits of the resident training rows over a grid of alphas (``fsnap_ridge_path``, K <= 144): the

@@ -2910,6 +2910,161 @@ int fsnap_loco_rows_uq(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, co
     return FSNAP_OK;
 }
 
+// ---- per-configuration influence vectors and the outer-product sums of the cluster-robust covariances (kernel L1 of
+// fsnap_loco.hip, kernels I0 / I1 / I2 of fsnap_influence.hip); fsnap_loco_rows's arguments and checks ------------------------
+
+int fsnap_influence_rows(fsnap_ctx* ctx, int mode, int64_t K, int64_t J, const double* M, const double* beta,
+                         const int32_t* sorted_rows, const int64_t* cfg_offsets, int64_t ncfg, double* pred_out,
+                         double* cfg_info_out, double* unit_out, double* S_out, double* V_out, double* Ws_out, double* Wv_out) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_influence_rows";
+    if (mode != FSNAP_INFL_SCORES && mode != FSNAP_INFL_FULL) return ctx->fail(FSNAP_E_ARG, "%s: mode = %d", who, mode);
+    const bool full = mode == FSNAP_INFL_FULL;
+    if (!M || !beta || !cfg_offsets || (ncfg > 0 && (!cfg_info_out || !unit_out)))
+        return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
+    if (!full && (V_out || Wv_out || pred_out))
+        return ctx->fail(FSNAP_E_ARG, "%s: V_out, Wv_out and pred_out need FSNAP_INFL_FULL", who);
+    if (K < 1 || K > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: K = %lld", who, (long long)K);
+    if (J < 1 || J > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: J = %lld", who, (long long)J);
+    if (ncfg < 0 || ncfg > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: ncfg = %lld", who, (long long)ncfg);
+    const int64_t m = ctx->m;
+    if (m > 0 && K != ctx->K)
+        return ctx->fail(FSNAP_E_ARG, "%s: K = %lld, the resident rows have %lld columns", who, (long long)K, (long long)ctx->K);
+    if (m > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: needs m < 2^31", who);
+    int rc = check_unit_index(ctx, who, "cfg_offsets", sorted_rows, cfg_offsets, ncfg, m, [](int64_t, int32_t) { return 0; });
+    if (rc) return rc;
+    const int64_t npos = cfg_offsets[ncfg];
+    if (Ws_out) std::fill(Ws_out, Ws_out + J * J, 0.0);
+    if (Wv_out) std::fill(Wv_out, Wv_out + J * J, 0.0);
+    if (ncfg == 0 || m == 0) return FSNAP_OK;
+    if (pred_out)
+        for (int64_t i = 0; i < m; ++i) pred_out[i] = std::numeric_limits<double>::quiet_NaN();
+    for (int64_t c = 0; c < ncfg; ++c) {      // configurations without rows; SCORES: every one (no factorisation, no pivot)
+        const int64_t n = cfg_offsets[c + 1] - cfg_offsets[c];
+        cfg_info_out[4 * c] = (double)std::min(n, J);
+        cfg_info_out[4 * c + 1] = std::numeric_limits<double>::infinity();
+        cfg_info_out[4 * c + 2] = 1.0;
+        cfg_info_out[4 * c + 3] = n <= J ? 1.0 : 0.0;
+        unit_out[3 * c] = unit_out[3 * c + 1] = unit_out[3 * c + 2] = 0.0;
+    }
+    if (S_out) std::fill(S_out, S_out + ncfg * J, 0.0);
+    if (V_out) std::fill(V_out, V_out + ncfg * J, 0.0);
+    if (npos == 0) return FSNAP_OK;
+    if ((rc = check_rows(ctx)) || (rc = check_weights(ctx))) return rc;
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    if (ctx->uq_inflight) {
+        FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+        ctx->uq_inflight = false;
+    }
+    int npk = 0;
+    if ((rc = ensure_wpack(ctx, &npk))) return rc;
+    const double* wpack = ctx->wpack_override ? ctx->wpack_override : (const double*)ctx->wpack.p;
+    // configurations by solve size d_c = min(n_c, J) as fsnap_loco_rows_uq bins them (kernel I1 runs the body with UQ = true)
+    const UnitBins bins = bin_units(
+        ncfg, [&](int64_t c) { return cfg_offsets[c + 1] - cfg_offsets[c]; }, J, fsnap::LOCO_MAX_LDS_D, ctx->num_cu,
+        [](int64_t dmax) { return dmax * dmax + 3 * dmax; }, ctx->loco_hlist);
+    const int64_t dmax = bins.dmax, hslice = dmax * dmax + 3 * dmax;
+    const int* nblk = bins.nblk;
+    const int64_t Kp = (K + 15) / 16 * 16, Jp = (J + 15) / 16 * 16;
+    const size_t nM = (size_t)(Kp * Jp);
+    ctx->loco_hM.assign(nM + (size_t)Kp, 0.0);
+    for (int64_t k = 0; k < K; ++k) std::memcpy(&ctx->loco_hM[(size_t)(k * Jp)], M + k * J, (size_t)J * 8);
+    std::memcpy(&ctx->loco_hM[nM], beta, (size_t)K * 8);
+    const int nvg = std::max({nblk[0], nblk[1], nblk[2], nblk[3], 1});
+    const int64_t ntiles = (Jp / 16) * (Jp / 16 + 1) / 2;
+    const bool want_ws = Ws_out != nullptr, want_wv = Wv_out != nullptr;
+    if ((want_ws || want_wv) && fsnap::infl_chunks(ncfg) * ntiles > 0x7FFFFFFF)
+        return ctx->fail(FSNAP_E_ARG, "%s: %lld units x %lld tiles are too many for one launch", who, (long long)ncfg, (long long)ntiles);
+    const size_t nUJ = (size_t)ncfg * (size_t)Jp;
+    if (!ctx->loco_M.ensure((nM + (size_t)Kp) * 8) || !ctx->loco_idx.ensure((size_t)npos * 4) ||
+        !ctx->loco_off.ensure((size_t)(ncfg + 1) * 8) || !ctx->loco_list.ensure(std::max<size_t>(ctx->loco_hlist.size(), 1) * 4) ||
+        !ctx->loco_Z.ensure((size_t)npos * (size_t)Jp * 8) || !ctx->loco_aux.ensure((size_t)npos * 3 * 8) ||
+        !ctx->infl_S.ensure(nUJ * 8) || !ctx->infl_unit.ensure((size_t)ncfg * 3 * 8) ||
+        ((want_ws || want_wv) && (!ctx->infl_part.ensure((size_t)(fsnap::infl_chunks(ncfg) * ntiles) * 256 * 8) ||
+                                  !ctx->infl_W.ensure((size_t)(2 * J * J) * 8))) ||
+        (full && (!ctx->loco_pred.ensure((size_t)m * 8) || !ctx->loco_info.ensure((size_t)ncfg * 4 * 8) ||
+                  !ctx->infl_V.ensure(nUJ * 8) || !ctx->loco_v.ensure((size_t)nvg * (size_t)Jp * 8) ||
+                  (nblk[3] > 0 && !ctx->loco_H.ensure((size_t)nblk[3] * (size_t)hslice * 8)))))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(influence) failed");
+    FSNAP_HIP(hipMemcpyAsync(ctx->loco_M.p, ctx->loco_hM.data(), (nM + (size_t)Kp) * 8, hipMemcpyHostToDevice, ctx->stream),
+              "hipMemcpy(M)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->loco_idx.p, sorted_rows, (size_t)npos * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(idx)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->loco_off.p, cfg_offsets, (size_t)(ncfg + 1) * 8, hipMemcpyHostToDevice, ctx->stream),
+              "hipMemcpy(offsets)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->loco_list.p, ctx->loco_hlist.data(), ctx->loco_hlist.size() * 4, hipMemcpyHostToDevice,
+                             ctx->stream),
+              "hipMemcpy(lists)");
+    // configurations without rows are in no list: their rows of S and V stay zero for kernel I2
+    FSNAP_HIP(hipMemsetAsync(ctx->infl_S.p, 0, nUJ * 8, ctx->stream), "hipMemset(S)");
+    if (full) {
+        FSNAP_HIP(hipMemsetAsync(ctx->infl_V.p, 0, nUJ * 8, ctx->stream), "hipMemset(V)");
+        FSNAP_HIP(hipMemsetAsync(ctx->loco_pred.p, 0xFF, (size_t)m * 8, ctx->stream), "hipMemset(pred)");   // all-ones: NaN
+    }
+    double* aux = (double*)ctx->loco_aux.p;
+    FSNAP_HIP(fsnap::launch_loco_zeta(ctx->dA, ctx->lda, (int)K, (const int*)ctx->loco_idx.p, npos, wpack,
+                                      (const double*)ctx->loco_M.p, (int)Jp, (const double*)ctx->loco_M.p + nM,
+                                      (double*)ctx->loco_Z.p, aux, aux + npos, aux + 2 * npos, ctx->stream),
+              "launch fsnap_loco_zeta_k");
+    if (full) {
+        size_t first = 0;
+        for (int b = 0; b < 4; ++b) {
+            const int ncl = (int)bins.lists[b].size();
+            if (ncl > 0)
+                FSNAP_HIP(fsnap::launch_infl_cfg(bins.D[b], nblk[b], (const double*)ctx->loco_Z.p, (int)Jp, (int)J, aux,
+                                                 aux + npos, aux + 2 * npos, (const int*)ctx->loco_idx.p,
+                                                 (const int64_t*)ctx->loco_off.p, (const int*)ctx->loco_list.p + first, ncl,
+                                                 (double*)ctx->loco_H.p, (int)dmax, (double*)ctx->loco_v.p,
+                                                 (double*)ctx->loco_pred.p, (double*)ctx->loco_info.p, (double*)ctx->infl_V.p,
+                                                 (double*)ctx->infl_S.p, (double*)ctx->infl_unit.p, ctx->stream),
+                          "launch fsnap_infl_cfg_k");
+            first += (size_t)ncl;
+        }
+    } else {
+        const int ncl = (int)ctx->loco_hlist.size();      // the four lists one after the other: every configuration with rows
+        FSNAP_HIP(fsnap::launch_infl_scores(std::min(ncl, std::max(1, 16 * ctx->num_cu)), (const double*)ctx->loco_Z.p, (int)Jp,
+                                            (int)J, aux, aux + npos, (const int64_t*)ctx->loco_off.p,
+                                            (const int*)ctx->loco_list.p, ncl, (double*)ctx->infl_S.p,
+                                            (double*)ctx->infl_unit.p, ctx->stream),
+                  "launch fsnap_infl_scores_k");
+    }
+    double* dW = (double*)ctx->infl_W.p;
+    if (want_ws) {
+        FSNAP_HIP(fsnap::launch_infl_outer((const double*)ctx->infl_S.p, ncfg, (int)Jp, (int)J, (double*)ctx->infl_part.p, dW,
+                                           ctx->stream),
+                  "launch fsnap_infl_outer_k");
+        FSNAP_HIP(hipMemcpyAsync(Ws_out, dW, (size_t)(J * J) * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(Ws)");
+    }
+    if (want_wv) {      // the same partials buffer: the stream orders the two sums
+        FSNAP_HIP(fsnap::launch_infl_outer((const double*)ctx->infl_V.p, ncfg, (int)Jp, (int)J, (double*)ctx->infl_part.p,
+                                           dW + J * J, ctx->stream),
+                  "launch fsnap_infl_outer_k");
+        FSNAP_HIP(hipMemcpyAsync(Wv_out, dW + J * J, (size_t)(J * J) * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(Wv)");
+    }
+    ctx->loco_hinfo.resize((size_t)ncfg * 7);
+    double* hunit = ctx->loco_hinfo.data() + (size_t)ncfg * 4;
+    if (pred_out)
+        FSNAP_HIP(hipMemcpyAsync(pred_out, ctx->loco_pred.p, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(pred)");
+    if (full)
+        FSNAP_HIP(hipMemcpyAsync(ctx->loco_hinfo.data(), ctx->loco_info.p, (size_t)ncfg * 32, hipMemcpyDeviceToHost, ctx->stream),
+                  "hipMemcpy(info)");
+    FSNAP_HIP(hipMemcpyAsync(hunit, ctx->infl_unit.p, (size_t)ncfg * 24, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(unit)");
+    if (S_out)
+        FSNAP_HIP(hipMemcpy2DAsync(S_out, (size_t)J * 8, ctx->infl_S.p, (size_t)Jp * 8, (size_t)J * 8, (size_t)ncfg,
+                                   hipMemcpyDeviceToHost, ctx->stream),
+                  "hipMemcpy(S)");
+    if (V_out)
+        FSNAP_HIP(hipMemcpy2DAsync(V_out, (size_t)J * 8, ctx->infl_V.p, (size_t)Jp * 8, (size_t)J * 8, (size_t)ncfg,
+                                   hipMemcpyDeviceToHost, ctx->stream),
+                  "hipMemcpy(V)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    for (int64_t c = 0; c < ncfg; ++c)
+        if (cfg_offsets[c + 1] > cfg_offsets[c]) {
+            if (full) std::memcpy(cfg_info_out + 4 * c, &ctx->loco_hinfo[(size_t)(4 * c)], 32);
+            std::memcpy(unit_out + 3 * c, hunit + 3 * c, 24);
+        }
+    return FSNAP_OK;
+}
+
 // ---- leave-one-unit-out refits over a grid of alphas (kernel P1 of fsnap_path.hip) ---------------------------------------
 
 int fsnap_ridge_path(fsnap_ctx* ctx, int64_t K, const double* G, const double* c, const double* alphas, int64_t Q,

@@ -141,6 +141,9 @@ struct fsnap_ctx {
     DevBuf loco_lev;                   // fsnap_loco_rows_uq: the leverage per row (its other buffers are those above)
     std::vector<double> loco_hM, loco_hinfo;
     std::vector<int32_t> loco_hlist;
+    // fsnap_influence_rows: V and S (ncfg x Jp each), the unit records (ncfg x 3), kernel I2's chunk partials and [W_s | W_v]
+    // (its other buffers are fsnap_loco_rows'); kept between calls
+    DevBuf infl_V, infl_S, infl_unit, infl_part, infl_W;
     // fsnap_ridge_path: [G | c | alphas], row classes, per-workgroup base tiles, sums, info, predictions (the unit index and
     // offsets share loco_idx / loco_off); kept between calls
     DevBuf path_in, path_cls, path_base, path_sums, path_info, path_pred;

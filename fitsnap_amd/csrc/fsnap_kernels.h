@@ -244,6 +244,25 @@ hipError_t launch_loco_uq_cfg(int D, int nblocks, const double* Z, int Jp, int J
                               const double* pb, const int* idx, const int64_t* off, const int* clist, int ncl, double* Hg,
                               int dmax, double* vg, double* pred, double* lev, double* info, hipStream_t st);
 
+// Influence vectors and outer-product sums (fsnap_influence.hip).  Kernel I1: launch_loco_cfg's geometry, predictions and info
+// (bit for bit), plus per unit c of the list V[c Jp ..] = v_c (zeros when not identifiable), S[c Jp ..] = s_c = Z_c^T e_c and
+// unit[3 c ..] = (|v_c|^2, |s_c|^2, s_c . v_c) (first and third NaN when not identifiable); columns J ... Jp - 1 of V and S are
+// written as zeros.  D = 0: Hg holds nblocks x (dmax^2 + 3 dmax) doubles.
+hipError_t launch_infl_cfg(int D, int nblocks, const double* Z, int Jp, int J, const double* pw, const double* pe,
+                           const double* pb, const int* idx, const int64_t* off, const int* clist, int ncl, double* Hg,
+                           int dmax, double* vg, double* pred, double* info, double* V, double* S, double* unit,
+                           hipStream_t st);
+// Kernel I0: S[c Jp ..] and unit[3 c ..] = (NaN, |s_c|^2, NaN) of the units clist[ncl] from kernel L1's Z, pw, pe alone; the bits
+// of kernel I1's S and |s_c|^2.
+hipError_t launch_infl_scores(int nblocks, const double* Z, int Jp, int J, const double* pw, const double* pe,
+                              const int64_t* off, const int* clist, int ncl, double* S, double* unit, hipStream_t st);
+// Kernel I2 and its fold: W (J x J, device) = X^T X of X (nunits x Jp, device; columns >= J are ignored), chunks of INFL_CHUNK
+// units in index order.  part: infl_chunks(nunits) x (Jp / 16)(Jp / 16 + 1) / 2 x 256 doubles of scratch.  nunits <= 0: nothing is
+// launched (W is left alone).
+constexpr int INFL_CHUNK = 512;
+inline int64_t infl_chunks(int64_t nunits) { return (nunits + INFL_CHUNK - 1) / INFL_CHUNK; }
+hipError_t launch_infl_outer(const double* X, int64_t nunits, int Jp, int J, double* part, double* W, hipStream_t st);
+
 // Leave-one-unit-out refits over a grid of alphas (fsnap_path.hip, kernel P1; K <= PATH_MAX_K).  For every unit u (positions
 // off[u] .. off[u + 1] of idx) and alpha_q: beta = (G - G_u + alpha_q I)^-1 (c - c_u) by a Jacobi-scaled blocked Cholesky,
 // sums[((q nunits + u) nclass + cls) 4 ..] = (n, sum |r|, sum r^2, sum (w r)^2) of r_i = b_i - a_i . beta over the unit's rows

@@ -25,7 +25,7 @@ import numpy as np
 
 from .. import _capi
 from .._hostblas import blas_threads
-from . import ard_path, lasso_path, loco, loco_uq, ridge_path, select, select_joint, uq
+from . import ard_path, influence, lasso_path, loco, loco_uq, ridge_path, select, select_joint, uq
 
 
 class _TrainWeights:
@@ -1170,6 +1170,36 @@ class Solver:
         ``units``, ``unidentifiable``).  Raises ValueError for solvers whose fit is not a linear smoother of the rows,
         for ``apply_transpose`` and when the noise cannot be resolved (no degrees of freedom left)."""
         return loco_uq.loco_predictive(self, by, fs_dict, b, w, noise, method)
+
+    # ------------------------------------------------------------------------------
+    # per-configuration influence and cluster-robust coefficient covariances (solvers/influence.py, csrc/fsnap_influence.hip)
+    # ------------------------------------------------------------------------------
+    def influence(self, by="Configs", fs_dict=None, b=None, w=None, kinds=("cr1", "jack"), noise=None, want_dfbeta=False,
+                  method="auto"):
+        """Which units move the coefficients, and how uncertain are the coefficients when the rows of one unit are
+        correlated?  From the leave-one-unit-out algebra of ``loco_errors`` (same labels ``fs_dict[by]``, truths, weights,
+        solvers and factor M; no refit): per unit the exact coefficient change of the refit without it, beta_{-c} - beta =
+        -M v_c, and the cluster-robust covariances of beta with clusters = units.  ``kinds``: which of "cr0" (the sandwich
+        M W_s M^T), "cr1" (its small-sample form U / (U - 1) (n - 1) / (n - p)) and "jack" (CR3, the delete-one-unit
+        jackknife (U' - 1) / U' M W_v M^T) to assemble next to ``classical`` = sigma^2 (G + alpha I)^-1.  Without "jack" and
+        ``want_dfbeta`` only the scores s_c are formed (no factorisation: cook and shift are NaN in the unit frame).
+        ``noise``: as in ``loco_predictive``.  ``method``: "device" (``fsnap_influence_rows``), "host" (the same closed
+        forms in numpy on the downloaded rows) or "auto" (device).  Collective on several ranks; every unit must live on
+        one rank.  Returns ``influence.InfluenceResult(units, cov, stderr, dfbeta, noise, unidentifiable)``: ``units`` a
+        DataFrame with one row per unit (label, group, rows, rows with w > 0, identifiable, d, smallest pivot, Cook's
+        distance |v_c|^2 / (p sigma^2), shift = |v_c|^2, score = |s_c|^2), pooled over the ranks; on rank 0 (None
+        elsewhere) ``cov``, a dict of K x K arrays in the rows' columns (no ``_offset`` B0 zeros, like ``self.cov``), and
+        ``stderr``, a DataFrame per coefficient (beta, se_<kind>, ratio_<kind> = se_<kind> / se_classical); ``dfbeta``
+        (``want_dfbeta`` only): -V M^T, one row per unit of THIS rank in the order of its units, K columns -- one GEMM on
+        the host over the downloaded V, not a kernel; DFBETAS is ``dfbeta / stderr["se_classical"]``.  Raises ValueError
+        for solvers whose fit is not a linear smoother of the rows, for ``apply_transpose`` and when the noise cannot be
+        resolved."""
+        return influence.influence(self, by, fs_dict, b, w, kinds, noise, want_dfbeta, method)
+
+    def use_covariance(self, cov):
+        """Make ``cov`` (K x K, e.g. ``influence().cov["cr1"]``) the covariance that ``prediction_variance``,
+        ``_compute_stdev`` and the selection methods read (``self.cov``)."""
+        self.cov = np.ascontiguousarray(cov, dtype=np.float64)
 
     # ------------------------------------------------------------------------------
     # leave-one-configuration-out error over a grid of ridge alphas (solvers/ridge_path.py, csrc/fsnap_path.hip)

@@ -382,6 +382,34 @@ int fsnap_loco_rows(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, const
 int fsnap_loco_rows_uq(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, const double* beta, const int32_t* sorted_rows,
                        const int64_t* cfg_offsets, int64_t ncfg, double* pred_out, double* lev_out, double* cfg_info_out);
 
+/* Per-configuration influence on the coefficients and the outer-product sums of the cluster-robust coefficient covariances
+ * (kernel L1 of csrc/fsnap_loco.hip, kernels I0 / I1 / I2 of csrc/fsnap_influence.hip, fp64 MFMA; no refit).  M, beta,
+ * sorted_rows, cfg_offsets, ncfg, their checks and error codes are those of fsnap_loco_rows.  With its notation, per
+ * configuration c:
+ *     s_c = Z_c^T e_c                         (J)  the score of the configuration in M space; needs no solve
+ *     v_c = (I_J - S_c)^-1 s_c                (J)  fsnap_loco_rows' v: the refit without c is beta_{-c} = beta - M v_c
+ *     W_s = sum_c s_c s_c^T,   W_v = sum_{c identifiable} v_c v_c^T        (J x J)
+ * so that M W_s M^T is the cluster-robust (CR0) covariance of beta and (U' - 1) / U' M W_v M^T its delete-one-configuration
+ * jackknife (CR3), U' the identifiable configurations.
+ * mode FSNAP_INFL_FULL (kernels L1, I1, I2): pred_out (m doubles, may be NULL) and cfg_info_out (ncfg x 4) are what
+ * fsnap_loco_rows writes for the same inputs, bit for bit; V_out (ncfg x J, may be NULL): v_c, zeros for a configuration that
+ * is not identifiable; S_out (ncfg x J, may be NULL): s_c, always; unit_out (ncfg x 3): (|v_c|^2, |s_c|^2, s_c . v_c), the
+ * first and third NaN for a configuration that is not identifiable; Ws_out, Wv_out (J x J each, may be NULL).
+ * mode FSNAP_INFL_SCORES (kernels L1, I0, I2; no factorisation): S_out, Ws_out as above; cfg_info_out = (d_c, inf, 1, n space)
+ * and unit_out = (NaN, |s_c|^2, NaN); V_out, Wv_out or pred_out given return FSNAP_E_ARG, as an unknown mode does.
+ * S_out, |s_c|^2 and Ws_out are the same bits in both modes: one loop over the configuration's rows forms s_c everywhere.
+ * A configuration without rows gets s = v = 0, info (0, inf, 1, 1) and unit_out zeros; ncfg = 0 or no resident rows give
+ * zero matrices and write nothing else.  The per-configuration outputs depend on the configuration's own rows alone:
+ * bit-identical run to run and under any permutation or subset of the configurations.  W_s and W_v add the configurations in
+ * index order, 4 per MFMA step in chunks of 512 whose partial sums are added in chunk order: bit-identical run to run, but
+ * NOT invariant under a permutation of the configurations.  No atomics.  Touches no resident rows, weights or sessions.
+ * Host in and out, synchronous. */
+#define FSNAP_INFL_SCORES 0   /* s_c, W_s only: kernels L1, I0, I2 */
+#define FSNAP_INFL_FULL 1     /* + v_c, W_v, pred: kernels L1, I1, I2 */
+int fsnap_influence_rows(fsnap_ctx* ctx, int mode, int64_t K, int64_t J, const double* M, const double* beta,
+                         const int32_t* sorted_rows, const int64_t* cfg_offsets, int64_t ncfg, double* pred_out,
+                         double* cfg_info_out, double* unit_out, double* S_out, double* V_out, double* Ws_out, double* Wv_out);
+
 /* Exact leave-one-unit-out errors of ridge fits over a grid of alphas from the resident training rows (kernel P1 of
  * csrc/fsnap_path.hip, fp64 MFMA; K <= 144).  G (host, K x K row-major; the lower triangle is read) and c (host, K) are the
  * statistics of the weighted rows x_i = w_i a_i, y_i = w_i b_i (w_i = 0 off the mask), alphas (host, Q doubles, finite, >= 0)
