@@ -123,6 +123,8 @@ SIGNATURES = {
     "fsnap_fit_candidates": (c_int, [c_void_p, c_int64, c_int, c_double, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p,
                                      c_void_p, POINTER(c_void_p)]),
     "fsnap_candidate_rows": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p]),
+    "fsnap_cv_candidates": (c_int, [c_void_p, c_int64, c_double, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p]),
+    "fsnap_cv_candidate_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int64, c_void_p]),
     "fsnap_row_variance": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "fsnap_row_variance_device": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
@@ -803,6 +805,33 @@ class HipContext:
         out = np.empty((P, int(ncat), 4) if what == CAND_ERROR_SUMS else (P, self.K))
         self._check(self._lib.fsnap_candidate_rows(self._h, int(layout), _ptr(beta), _ptr(Sa), int(P), int(ncat), self.K,
                                                    int(what), _ptr(out)))
+        return out
+
+    def cv_candidates(self, layout: int, alpha: float, S, F: int, K: int):
+        """The P x F leave-one-fold-out refits of the candidates S (P, C) from the per-(fold, category) statistics the
+        context holds for ``layout`` (``fsnap_cv_candidates``, K <= 144): (coef (P, F, K), info (P, F, 4): status, smallest
+        scaled pivot, live columns, weighted training rows).  A failed problem has status 1 and NaN coefficients."""
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        if S.ndim != 2:
+            raise ValueError("S must be (P, C)")
+        P, C = S.shape
+        F, K = int(F), int(K)
+        coef = np.empty((P, max(F, 0), max(K, 0)))
+        info = np.empty((P, max(F, 0), 4))
+        self._check(self._lib.fsnap_cv_candidates(self._h, int(layout), float(alpha), _ptr(S) if S.size else None, int(P), F,
+                                                  int(C), K, _ptr(coef) if coef.size else None, _ptr(info) if info.size else None))
+        return coef, info
+
+    def cv_candidate_rows(self, layout: int, coef, C: int):
+        """Held-out sums of P x F refits (``fsnap_cv_candidate_rows``): every categorised row of composite category
+        fold * C + c against coef[p, fold]; (P, F * C, 4) = sum|r|, sum r^2, sum|w0 r|, sum (w0 r)^2."""
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        if coef.ndim != 3 or coef.shape[2] != self.K:
+            raise ValueError(f"coef must have shape (P, F, {self.K})")
+        P, F, _ = coef.shape
+        out = np.empty((P, F * int(C), 4))
+        self._check(self._lib.fsnap_cv_candidate_rows(self._h, int(layout), _ptr(coef) if coef.size else None, int(P), int(F),
+                                                      int(C), self.K, _ptr(out) if out.size else None))
         return out
 
     # -- row-space least squares --------------------------------------------------------

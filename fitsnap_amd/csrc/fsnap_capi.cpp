@@ -3247,6 +3247,95 @@ int fsnap_ard_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const dou
     return FSNAP_OK;                                        // a failed problem is its own status 1, not the call's
 }
 
+// ---- grouped K-fold cross-validation of weight candidates (kernels V0, V1, V2 of fsnap_cv.hip) -----------------------------
+
+int fsnap_cv_candidates(fsnap_ctx* ctx, int64_t layout, double alpha, const double* S, int P, int F, int C, int64_t K,
+                        double* coef_out, double* info_out) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_cv_candidates";
+    if (!S || !coef_out || !info_out) return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
+    if (K < 1 || K > fsnap::CV_MAX_K) return ctx->fail(FSNAP_E_ARG, "%s: K = %lld (1 ... %d)", who, (long long)K, fsnap::CV_MAX_K);
+    if (F < 2 || C < 1 || P < 1) return ctx->fail(FSNAP_E_ARG, "%s: P = %d, F = %d, C = %d", who, P, F, C);
+    if (!std::isfinite(alpha) || alpha < 0.0) return ctx->fail(FSNAP_E_ARG, "%s: alpha = %g is negative or not finite", who, alpha);
+    if (layout <= 0 || layout != ctx->cand_layout || ctx->cand_stats_K <= 0 || !ctx->cand_stats.p)
+        return ctx->fail(FSNAP_E_STATE, "%s: no per-category statistics of layout %lld on the context (fsnap_cat_prepare + "
+                                        "fsnap_cat_normal_eq first)", who, (long long)layout);
+    if ((int64_t)F * C != ctx->cand_ncat || K != ctx->cand_stats_K)
+        return ctx->fail(FSNAP_E_ARG, "%s: F * C = %lld, K = %lld but the statistics have %d categories of order %lld", who,
+                         (long long)F * C, (long long)K, ctx->cand_ncat, (long long)ctx->cand_stats_K);
+    const int64_t nprob = (int64_t)P * F;
+    if (nprob > FSNAP_CV_MAX_PROBLEMS || (double)nprob * (double)K * 8.0 > (double)FSNAP_CAT_STATS_MAX_BYTES)
+        return ctx->fail(FSNAP_E_ARG, "%s: P * F = %lld problems of %lld coefficients (at most %d problems, "
+                                      "FSNAP_CAT_STATS_MAX_BYTES of coefficients)", who, (long long)nprob, (long long)K,
+                         FSNAP_CV_MAX_PROBLEMS);
+    for (int64_t i = 0; i < (int64_t)P * C; ++i)
+        if (!std::isfinite(S[i]))
+            return ctx->fail(FSNAP_E_ARG, "%s: S[%lld][%lld] is not finite", who, (long long)(i / C), (long long)(i % C));
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    const int64_t T = FSNAP_PACKED_LEN(K);
+    if (!ctx->cv_total.ensure((size_t)(C + (int64_t)F * C) * T * 8) || !ctx->cv_S.ensure((size_t)P * C * 8) ||
+        !ctx->cv_coef.ensure((size_t)nprob * K * 8) || !ctx->cv_info.ensure((size_t)nprob * 4 * 8))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(candidate cross-validation) failed");
+    FSNAP_HIP(hipMemcpyAsync(ctx->cv_S.p, S, (size_t)P * C * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(S)");
+    double* total = (double*)ctx->cv_total.p;
+    double* rest = total + (int64_t)C * T;                 // F C blocks: T[c] - B[f][c]
+    FSNAP_HIP(fsnap::launch_cv_total((const double*)ctx->cand_stats.p, F, C, (int)K, total, rest, ctx->stream),
+              "launch fsnap_cv_total_k");
+    const int nblocks = (int)std::min<int64_t>(nprob, (int64_t)fsnap::cv_blocks_per_cu((int)K) * std::max(1, ctx->num_cu));
+    FSNAP_HIP(fsnap::launch_cv_solve(nblocks, rest, total, (const double*)ctx->cv_S.p, P, F, C, (int)K, alpha, (double*)ctx->cv_coef.p,
+                                     (double*)ctx->cv_info.p, ctx->stream),
+              "launch fsnap_cv_solve_k");
+    FSNAP_HIP(hipMemcpyAsync(coef_out, ctx->cv_coef.p, (size_t)nprob * K * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(coef)");
+    FSNAP_HIP(hipMemcpyAsync(info_out, ctx->cv_info.p, (size_t)nprob * 4 * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(info)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    return FSNAP_OK;                                        // a failed problem is its own status 1, not the call's
+}
+
+int fsnap_cv_candidate_rows(fsnap_ctx* ctx, int64_t layout, const double* coef, int P, int F, int C, int64_t K_, double* out) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_cv_candidate_rows";
+    int rc;
+    if ((rc = check_rows(ctx)) || (rc = cand_check_layout(ctx, layout, who))) return rc;
+    if (!coef || !out || P < 1 || F < 1 || C < 1) return ctx->fail(FSNAP_E_ARG, "%s: bad argument", who);
+    if ((int64_t)F * C != ctx->cand_ncat || K_ != ctx->K)
+        return ctx->fail(FSNAP_E_ARG, "%s: F * C = %lld, K = %lld but the layout has %d categories, the rows %lld columns", who,
+                         (long long)F * C, (long long)K_, ctx->cand_ncat, (long long)ctx->K);
+    const int K = (int)ctx->K, ncat = ctx->cand_ncat;
+    const int64_t K8 = (K + 7) / 8 * 8;
+    if ((int64_t)P * F > FSNAP_CV_MAX_PROBLEMS || (double)F * (double)K8 * 16.0 * 8.0 > (double)FSNAP_CAT_STATS_MAX_BYTES)
+        return ctx->fail(FSNAP_E_ARG, "%s: P * F = %lld problems, F = %d coefficient tables of %lld x 16", who,
+                         (long long)P * F, F, (long long)K8);
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    const int64_t nch = ctx->cand_nch_a, nout = (int64_t)ncat * 4;
+    const int64_t per = fsnap::cand_rows_partial_doubles(FSNAP_CAND_ERROR_SUMS, K);
+    if (!ctx->cv_betaT.ensure((size_t)F * K8 * 16 * 8) || !ctx->cand_rpart.ensure((size_t)(nch > 0 ? nch : 1) * per * 8) ||
+        !ctx->cand_res.ensure((size_t)P * nout * 8))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(candidate cross-validation rows) failed");
+    if (nch == 0) FSNAP_HIP(hipMemsetAsync(ctx->cand_res.p, 0, (size_t)P * nout * 8, ctx->stream), "hipMemsetAsync");
+    std::vector<double> bt((size_t)F * K8 * 16);
+    for (int p0 = 0; p0 < P && nch > 0; p0 += fsnap::CAND_ROWS_MAX_P) {
+        const int np = std::min(fsnap::CAND_ROWS_MAX_P, P - p0);
+        std::fill(bt.begin(), bt.end(), 0.0);
+        for (int f = 0; f < F; ++f)
+            for (int p = 0; p < np; ++p)
+                for (int k = 0; k < K; ++k)
+                    bt[((size_t)f * K8 + k) * 16 + p] = coef[((int64_t)(p0 + p) * F + f) * K + k];
+        // the launch before may still read the tables: the copy is ordered after it on the stream
+        FSNAP_HIP(hipMemcpyAsync(ctx->cv_betaT.p, bt.data(), bt.size() * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(coef)");
+        FSNAP_HIP(fsnap::launch_cv_rows(ctx->dA, ctx->lda, ctx->db, (const double*)ctx->cand_w0.p, (const int*)ctx->cand_idx_a.p,
+                                        (const fsnap::CatChunk*)ctx->cand_ch_a.p, nch, K, C, (const double*)ctx->cv_betaT.p,
+                                        (double*)ctx->cand_rpart.p, ctx->stream),
+                  "launch fsnap_cv_rows_k");
+        FSNAP_HIP(fsnap::launch_cand_reduce(FSNAP_CAND_ERROR_SUMS, (const double*)ctx->cand_rpart.p, (const int*)ctx->cand_cb_a.p,
+                                            nullptr, ncat, np, p0, K, (double*)ctx->cand_res.p, ctx->stream),
+                  "launch fsnap_cand_reduce_k");
+        FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");   // bt is rewritten for the next group
+    }
+    FSNAP_HIP(hipMemcpyAsync(out, ctx->cand_res.p, (size_t)P * nout * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(out)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    return FSNAP_OK;
+}
+
 // ---- joint information-gain / variance-reduction scores of units (kernels J1, J2 of fsnap_joint.hip) ------------------
 
 namespace {

@@ -152,6 +152,9 @@ struct fsnap_ctx {
     // fsnap_ard_path: hyper-parameters, coefficients, lambdas, info, held-out sums (the fold sums live in lasso_sys); kept
     // between calls
     DevBuf ard_hyper, ard_coef, ard_lambda, ard_info, ard_held;
+    // fsnap_cv_candidates / fsnap_cv_candidate_rows: per-category totals followed by the F C blocks total - fold, scales, coefficients, info, the per-fold coefficient
+    // tables of a launch (the chunk partials and sums share cand_rpart / cand_res); kept between calls
+    DevBuf cv_total, cv_S, cv_coef, cv_info, cv_betaT;
     // fsnap_joint_*: the session's unit-sorted row index, unit offsets and per-position weights (uploaded once by begin), the
     // padded factor [M | M B] and B, Z / Pi per position (npos x Wp), the bucketed list of live units, per-unit (gain, reduction)
     // and info, per-workgroup scratch (S and the right-hand-side fragments of units too large for LDS); the host keeps the

@@ -307,6 +307,25 @@ int ard_blocks_per_cu(int K);
 hipError_t launch_ard_path(int nblocks, const double* folds, const double* total, const double* hyper, int K, int F, int Q,
                            int max_iter, double tol, double* coef, double* lambda, double* info, double* heldout, hipStream_t st);
 
+// Grouped K-fold cross-validation of weight candidates (fsnap_cv.hip; V1: K <= CV_MAX_K) on the F * C packed blocks of
+// fsnap_cat_normal_eq with composite category f * C + c.  Kernel V0: total[c] = sum_f stats[f * C + c], folds in index order,
+// and rest[f * C + c] = total[c] - stats[f * C + c] (F C blocks).
+// Kernel V1: problem p * F + f is the Jacobi-scaled Cholesky solve of Qm + alpha I, Qm = sum_c S[p][c]^2 rest[f * C + c]
+// (c ascending, one fma per term), over the live columns (dead: sum_c S^2 total[c].G_jj == 0 or Qm_jj <=
+// LOCO_PIVOT_TOL times it); a scaled pivot that is not > LOCO_PIVOT_TOL ends the problem with status 1 and NaN coefficients.
+// coef[P F][K], info[P F][4] = (status, smallest scaled pivot, live columns, sum_c S^2 (total.n - stats.n)).  One workgroup
+// of 256 threads per problem, nblocks workgroups stride over the problems.  Kernel V2: the chunks of the layout times the
+// coefficient table of their fold, betaT[F][K8][16] (K8 = K rounded up to 8; zero-padded), partials as launch_cand_rows
+// (what = 0) leaves them, for launch_cand_reduce (what = 0) with ncat = F C.  All pointers: device.
+constexpr int CV_MAX_K = 144;
+size_t cv_lds_bytes(int K);
+int cv_blocks_per_cu(int K);
+hipError_t launch_cv_total(const double* stats, int F, int C, int K, double* total, double* rest, hipStream_t st);
+hipError_t launch_cv_solve(int nblocks, const double* rest, const double* total, const double* S, int P, int F, int C, int K,
+                           double alpha, double* coef, double* info, hipStream_t st);
+hipError_t launch_cv_rows(const double* A, int64_t lda, const double* b, const double* w0, const int* idx, const CatChunk* chunks,
+                          int64_t nchunks, int K, int C, const double* betaT, double* partial, hipStream_t st);
+
 // Joint unit scores (fsnap_joint.hip).  Kernel J1: for the npos positions of the unit-sorted row index idx,
 // ZP[p] = om[p] a_idx[p] [M | M B] (Wp doubles per position; Fp: device, Kp x Wp row-major, zero-padded: columns [0, Jp) the
 // factor M, columns [Jp, Wp) the target block M B; Wp = Jp without a target; om: the weight of every position).

@@ -134,6 +134,8 @@ class CandidateFits:
         self.info = []
         self._layout = None          # tag of this object's category layout on the context (fsnap_cat_prepare)
         self._packed = None          # (context, device address, K, P) of the last fit's packed candidate statistics
+        self._cv = None              # (tag, composite categories, F) of cross_validate's fold x category layout
+        self._cv_folds = None        # (key, composite categories, fold_of_unit, F, rows per composite category) of its last folds
 
     @staticmethod
     def _categories(fs_dict, m):
@@ -203,6 +205,53 @@ class CandidateFits:
                 self._stats = ctx.cat_normal_eq(layout)
             self._layout = layout
         return ctx
+
+    def _cv_device(self, ccat, F):
+        """The composite layout fold x category of ``cross_validate`` and its statistics on this rank's GPU, under its own
+        tag (``self._cv``, next to ``self._layout``): prepared again whenever the context holds another layout or the folds
+        changed.  Collective in a multi-rank job, as ``_device`` is."""
+        ctx = self.pt.hip()
+        held = self._cv
+        stale = (held is None or held[2] != F or ctx.cat_info()["layout"] != held[0]
+                 or not (held[1] is ccat or np.array_equal(held[1], ccat)))
+        if self.pt.multi:
+            flag = np.array([1.0 if stale else 0.0])
+            self.pt.allreduce_host(flag, _capi.REDUCE_MAX)
+            stale = bool(flag[0] > 0)
+        if stale:
+            tag = 0
+            if self.m > 0:
+                ctx = self._push_base()
+                tag = ctx.cat_prepare(ccat, F * self.ncat)
+            if self.pt.multi:
+                tag, _ = ctx.cat_normal_eq_dist(tag, self.K, F * self.ncat)
+            else:
+                ctx.cat_normal_eq(tag)
+            self._cv = (tag, ccat, F)
+        return ctx
+
+    def cross_validate(self, S, folds=5, by="Configs", seed=0, method="auto"):
+        """Grouped K-fold cross-validation of the candidates S (P x ncat): the units ``fs_dict[by]`` of the training rows
+        are dealt into folds (``folds``: an int F, ``None`` for one fold per unit, or a mapping unit -> fold; ``seed`` as in
+        ``lasso_path.deal_folds``), every candidate is refitted with each fold left out, and every training row is scored
+        under the refit that did not see its unit.  Returns a ``CandidateCV`` (solvers/candidates_cv.py): ``coef`` (P, F, K),
+        ``status``, ``min_pivot``, ``route``, ``fold_of_unit``, pooled ``sums`` (P, ncat, 5), ``tables()``,
+        ``row_type_errors`` and ``cost(weights, metric)`` -- the weight search's objective on held-out rows.
+
+        The refits are plain Jacobi-scaled Cholesky solves of the normal equations (alpha = [RIDGE] alpha, 0 for SVD); they
+        are not ``fit``'s chain of probe, refinement and row-space fallback.  ``method="device"``: kernels V1 + V2 of
+        csrc/fsnap_cv.hip (K <= 144), failed problems stay NaN with status 1; ``"composed"``: ``fsnap_fit_candidates`` on
+        the composite layout with scales that are zero on the held-out fold, then ``fsnap_candidate_rows``; ``"auto"``: the
+        device route with its status-1 problems solved again by the composed one, the composed route beyond 144 columns.
+
+        A context holds ONE category layout: this call prepares the composite layout fold x category under its own tag, and
+        the next ``fit`` / ``errors`` prepares this object's own layout again.  Repeated calls with the same folds reuse the
+        composite layout and its statistics.  Collective in a multi-rank job: a unit gets one fold on every rank, the
+        statistics are summed over the ranks and so are the pooled sums, on every rank.  KeyError without ``fs_dict[by]``;
+        ValueError when F x ncat blocks of statistics pass FSNAP_CAT_STATS_MAX_BYTES."""
+        from . import candidates_cv
+
+        return candidates_cv.cross_validate(self, S, folds, by, seed, method)
 
     # ------------------------------------------------------------------------------
     def fit(self, S):

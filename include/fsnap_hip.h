@@ -746,6 +746,41 @@ int fsnap_fit_candidates(fsnap_ctx* ctx, int64_t layout, int kind, double param,
 int fsnap_candidate_rows(fsnap_ctx* ctx, int64_t layout, const double* beta, const double* S, int P, int ncat, int64_t K,
                          int what, double* out);
 
+/* Grouped K-fold cross-validation of weight candidates on per-(fold, category) statistics (kernels V0, V1 of
+ * csrc/fsnap_cv.hip; the folds, routes and tables are solvers/candidates_cv.py).  The context holds, for `layout`, F * C
+ * packed blocks B[f][c] as fsnap_cat_normal_eq / fsnap_cat_normal_eq_dist leave them, composite category f * C + c (fold f of
+ * the row's unit, category c of the weight search); T[c] = sum_f B[f][c], folds added in index order.  S (host, P x C,
+ * row-major, finite) scales category c of candidate p.  Problem (p, f), 0 <= f < F, is the refit of candidate p without fold f:
+ *     Qm = sum_c S[p][c]^2 (T[c].G - B[f][c].G),  qv = sum_c S[p][c]^2 (T[c].r - B[f][c].r)     (c ascending, one fma per term)
+ *     Tp_jj = sum_c S[p][c]^2 T[c].G_jj
+ *     H = Qm + alpha I,  D = sqrt(diag H),  beta = D^-1 (D^-1 H D^-1)^-1 D^-1 qv                 (Cholesky, live columns only)
+ * Column j is dead -- coefficient 0, its row, column and qv_j removed -- when Tp_jj == 0 or Qm_jj <= 1e-10 Tp_jj (the fold
+ * alone touched the column and the subtraction left noise: the rule of fsnap_lasso_path).  A pivot of the scaled matrix that
+ * is not > 1e-10 ends the problem with status 1 and NaN coefficients (the rule of fsnap_ridge_path); the call still returns
+ * FSNAP_OK.  These are plain Jacobi-scaled Cholesky solves of the normal equations: no probe, no refinement with the row
+ * residual, no row-space solve.  Outputs (host): coef_out[P][F][K]; info_out[P][F][4] = status (0 / 1), the smallest scaled
+ * pivot met (inf when no column is live), live columns, sum_c S[p][c]^2 (T[c].n - B[f][c].n) (the training rows of the
+ * problem, each counted with the square of its category's scale).  FSNAP_E_ARG: K outside 1 ... 144 or not the order of the
+ * statistics, F < 2, C < 1, P < 1, F * C != the layout's number of categories, a non-finite S or a negative or non-finite
+ * alpha, a NULL pointer, P * F > FSNAP_CV_MAX_PROBLEMS or P * F * K doubles past FSNAP_CAT_STATS_MAX_BYTES.  FSNAP_E_STATE:
+ * the context no longer holds the layout or its statistics.  fp64, no atomics; every sum runs in an order fixed by the
+ * problem alone: a problem's bits do not depend on the batch, the grid or the run.  The resident rows, weights, mask, the
+ * layout and its statistics are not touched.  Synchronous. */
+#define FSNAP_CV_MAX_PROBLEMS (1 << 20)
+int fsnap_cv_candidates(fsnap_ctx* ctx, int64_t layout, double alpha, const double* S, int P, int F, int C, int64_t K,
+                        double* coef_out, double* info_out);
+
+/* Held-out sums of the refits above (kernel V2 of csrc/fsnap_cv.hip, reduced by kernel C3R of csrc/fsnap_cand.hip): one pass
+ * over the categorised rows of `layout` per 16 candidates.  A chunk of the layout holds rows of ONE composite category, so of
+ * one fold f = category / C; its rows are multiplied with coef[p][f] (host, P x F x K), r = t - a . coef[p][f]: the row's
+ * residual under the refit that did not see its unit.  out (host): P x (F * C) x 4 = sum|r|, sum r^2, sum|w0 r|, sum (w0 r)^2
+ * per candidate and composite category, chunks and their waves added in index order; the weighted sums scale with |S[p][c]|
+ * and S[p][c]^2.  NaN coefficients give NaN sums for that (p, f) only.  K must be the width of the resident rows (any K) and
+ * F * C the layout's number of categories, else FSNAP_E_ARG; FSNAP_E_STATE when the context no longer holds the layout.
+ * Bit-identical run to run; a candidate's sums do not depend on the other candidates.  Nothing resident is changed.
+ * Synchronous. */
+int fsnap_cv_candidate_rows(fsnap_ctx* ctx, int64_t layout, const double* coef, int P, int F, int C, int64_t K, double* out);
+
 /* ---- multi-GPU: one process per GPU; RCCL or one-shot peer-to-peer over xGMI -------- */
 
 /* The reference's data-parallel form of this path (examples/library/transpose_trick/example.py:230-254): every MPI
