@@ -2721,6 +2721,104 @@ UnitBins bin_units(int64_t count, Size&& size, int64_t J, int lds_max, int num_c
     return bins;
 }
 
+// One launch per bin that has units: launch(D, workgroups, where the bin's list starts in the four lists, its units).
+template <class Launch>
+hipError_t launch_bins(const UnitBins& bins, Launch&& launch) {
+    size_t first = 0;
+    for (int b = 0; b < 4; ++b) {
+        const int ncl = (int)bins.lists[b].size();
+        if (ncl > 0)
+            if (const hipError_t e = launch(bins.D[b], bins.nblk[b], first, ncl)) return e;
+        first += (size_t)ncl;
+    }
+    return hipSuccess;
+}
+
+// What a pass over the resident rows with kernel 1A's pairs begins with: the context's device, the copies out of
+// fsnap_row_variance's staging drained (once), the pairs current.  *wpack: the pairs to read.
+int resident_weights(fsnap_ctx* ctx, const double** wpack) {
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    if (ctx->uq_inflight) {
+        FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+        ctx->uq_inflight = false;
+    }
+    int npk = 0;
+    if (const int rc = ensure_wpack(ctx, &npk)) return rc;
+    *wpack = ctx->wpack_override ? ctx->wpack_override : (const double*)ctx->wpack.p;
+    return FSNAP_OK;
+}
+
+// The front that fsnap_loco_rows, fsnap_loco_rows_uq and fsnap_influence_rows share.  unit_pass_check: their common
+// arguments against the resident rows.  unit_pass_stage (there is a position: npos > 0) queues everything up to kernel L1 and
+// owns loco_hM / loco_hlist and loco_M / idx / off / list / Z / aux, of which UnitPass is the typed view; the outputs,
+// loco_v, loco_H and the infl_* buffers are the entry point's own.
+struct UnitPass {
+    const double *Z, *pw, *pe, *pb;    // kernel L1's results per position: zeta (Jp doubles), w_eff, e, a . beta
+    const int* idx;                    // on the device: the sorted row index, the configuration offsets, the bins' lists
+    const int64_t* off;
+    const int* lists;
+    int Jp;                            // J in 16-multiples
+    UnitBins bins;                     // configurations by solve size d_c = min(n_c, J)
+    int dmax;                          // general path (bin 3): one slice of hslice = scratch_doubles(dmax) per workgroup
+    int64_t hslice;
+    int nvg;                           // the most workgroups of any bin's launch
+};
+
+int unit_pass_check(fsnap_ctx* ctx, const char* who, int64_t K, int64_t J, const int32_t* sorted_rows, const int64_t* cfg_offsets,
+                    int64_t ncfg) {
+    if (K < 1 || K > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: K = %lld", who, (long long)K);
+    if (J < 1 || J > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: J = %lld", who, (long long)J);
+    if (ncfg < 0 || ncfg > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: ncfg = %lld", who, (long long)ncfg);
+    const int64_t m = ctx->m;
+    if (m > 0 && K != ctx->K)
+        return ctx->fail(FSNAP_E_ARG, "%s: K = %lld, the resident rows have %lld columns", who, (long long)K, (long long)ctx->K);
+    if (m > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: needs m < 2^31", who);
+    return check_unit_index(ctx, who, "cfg_offsets", sorted_rows, cfg_offsets, ncfg, m, [](int64_t, int32_t) { return 0; });
+}
+
+int unit_pass_stage(fsnap_ctx* ctx, const char* label, int64_t K, int64_t J, const double* M, const double* beta,
+                    const int32_t* sorted_rows, const int64_t* cfg_offsets, int64_t ncfg, int64_t (*scratch_doubles)(int64_t),
+                    UnitPass* pass) {
+    int rc;
+    if ((rc = check_rows(ctx)) || (rc = check_weights(ctx))) return rc;
+    const double* wpack = nullptr;
+    if ((rc = resident_weights(ctx, &wpack))) return rc;
+    UnitBins bins = bin_units(
+        ncfg, [&](int64_t c) { return cfg_offsets[c + 1] - cfg_offsets[c]; }, J, fsnap::LOCO_MAX_LDS_D, ctx->num_cu,
+        scratch_doubles, ctx->loco_hlist);
+    const int64_t npos = cfg_offsets[ncfg], dmax = bins.dmax;
+    const int nvg = std::max({bins.nblk[0], bins.nblk[1], bins.nblk[2], bins.nblk[3], 1});
+    const int64_t Kp = (K + 15) / 16 * 16, Jp = (J + 15) / 16 * 16;
+    const size_t nM = (size_t)(Kp * Jp);
+    ctx->loco_hM.assign(nM + (size_t)Kp, 0.0);
+    for (int64_t k = 0; k < K; ++k) std::memcpy(&ctx->loco_hM[(size_t)(k * Jp)], M + k * J, (size_t)J * 8);
+    std::memcpy(&ctx->loco_hM[nM], beta, (size_t)K * 8);
+    if (!ctx->loco_M.ensure((nM + (size_t)Kp) * 8) || !ctx->loco_idx.ensure((size_t)npos * 4) ||
+        !ctx->loco_off.ensure((size_t)(ncfg + 1) * 8) || !ctx->loco_list.ensure(ctx->loco_hlist.size() * 4) ||
+        !ctx->loco_Z.ensure((size_t)npos * (size_t)Jp * 8) || !ctx->loco_aux.ensure((size_t)npos * 3 * 8))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(%s) failed", label);
+    FSNAP_HIP(hipMemcpyAsync(ctx->loco_M.p, ctx->loco_hM.data(), (nM + (size_t)Kp) * 8, hipMemcpyHostToDevice, ctx->stream),
+              "hipMemcpy(M)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->loco_idx.p, sorted_rows, (size_t)npos * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(idx)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->loco_off.p, cfg_offsets, (size_t)(ncfg + 1) * 8, hipMemcpyHostToDevice, ctx->stream),
+              "hipMemcpy(offsets)");
+    // npos > 0: a configuration has rows, so there is a list
+    FSNAP_HIP(hipMemcpyAsync(ctx->loco_list.p, ctx->loco_hlist.data(), ctx->loco_hlist.size() * 4, hipMemcpyHostToDevice,
+                             ctx->stream),
+              "hipMemcpy(lists)");
+    double* aux = (double*)ctx->loco_aux.p;
+    FSNAP_HIP(fsnap::launch_loco_zeta(ctx->dA, ctx->lda, (int)K, (const int*)ctx->loco_idx.p, npos, wpack,
+                                      (const double*)ctx->loco_M.p, (int)Jp, (const double*)ctx->loco_M.p + nM,
+                                      (double*)ctx->loco_Z.p, aux, aux + npos, aux + 2 * npos, ctx->stream),
+              "launch fsnap_loco_zeta_k");
+    // The entry point sizes and clears its own buffers from here on, so its memsets follow kernel L1 on the stream.  Either
+    // order gives the same result: kernel L1 neither reads nor writes those buffers.
+    *pass = UnitPass{(const double*)ctx->loco_Z.p, aux, aux + npos, aux + 2 * npos, (const int*)ctx->loco_idx.p,
+                     (const int64_t*)ctx->loco_off.p, (const int*)ctx->loco_list.p, (int)Jp, std::move(bins), (int)dmax,
+                     scratch_doubles(dmax), nvg};
+    return FSNAP_OK;
+}
+
 }  // namespace
 
 // ---- leave-one-configuration-out predictions of the resident training rows (kernels L1, L2 of fsnap_loco.hip) --------
@@ -2731,16 +2829,9 @@ int fsnap_loco_rows(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, const
     const char* who = "fsnap_loco_rows";
     if (!M || !beta || !cfg_offsets || !pred_out || (ncfg > 0 && !cfg_info_out))
         return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
-    if (K < 1 || K > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: K = %lld", who, (long long)K);
-    if (J < 1 || J > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: J = %lld", who, (long long)J);
-    if (ncfg < 0 || ncfg > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: ncfg = %lld", who, (long long)ncfg);
-    const int64_t m = ctx->m;
-    if (m > 0 && K != ctx->K)
-        return ctx->fail(FSNAP_E_ARG, "%s: K = %lld, the resident rows have %lld columns", who, (long long)K, (long long)ctx->K);
-    if (m > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: needs m < 2^31", who);
-    int rc = check_unit_index(ctx, who, "cfg_offsets", sorted_rows, cfg_offsets, ncfg, m, [](int64_t, int32_t) { return 0; });
+    int rc = unit_pass_check(ctx, who, K, J, sorted_rows, cfg_offsets, ncfg);
     if (rc) return rc;
-    const int64_t npos = cfg_offsets[ncfg];
+    const int64_t m = ctx->m, npos = cfg_offsets[ncfg];
     for (int64_t i = 0; i < m; ++i) pred_out[i] = std::numeric_limits<double>::quiet_NaN();
     for (int64_t c = 0; c < ncfg; ++c) {      // empty configurations: nothing to leave out
         cfg_info_out[4 * c] = 0.0;
@@ -2749,60 +2840,21 @@ int fsnap_loco_rows(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, const
         cfg_info_out[4 * c + 3] = 1.0;
     }
     if (npos == 0) return FSNAP_OK;
-    if ((rc = check_rows(ctx)) || (rc = check_weights(ctx))) return rc;
-    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-    if (ctx->uq_inflight) {
-        FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-        ctx->uq_inflight = false;
-    }
-    int npk = 0;
-    if ((rc = ensure_wpack(ctx, &npk))) return rc;
-    const double* wpack = ctx->wpack_override ? ctx->wpack_override : (const double*)ctx->wpack.p;
-    // configurations by solve size d_c = min(n_c, J); general path: one (dmax^2 + dmax) slice of scratch per workgroup
-    const UnitBins bins = bin_units(
-        ncfg, [&](int64_t c) { return cfg_offsets[c + 1] - cfg_offsets[c]; }, J, fsnap::LOCO_MAX_LDS_D, ctx->num_cu,
-        [](int64_t dmax) { return dmax * dmax + dmax; }, ctx->loco_hlist);
-    const int64_t dmax = bins.dmax, hslice = dmax * dmax + dmax;
-    const int* nblk = bins.nblk;
-    const int64_t Kp = (K + 15) / 16 * 16, Jp = (J + 15) / 16 * 16;
-    const size_t nM = (size_t)(Kp * Jp);
-    ctx->loco_hM.assign(nM + (size_t)Kp, 0.0);
-    for (int64_t k = 0; k < K; ++k) std::memcpy(&ctx->loco_hM[(size_t)(k * Jp)], M + k * J, (size_t)J * 8);
-    std::memcpy(&ctx->loco_hM[nM], beta, (size_t)K * 8);
-    const int nvg = std::max({nblk[0], nblk[1], nblk[2], nblk[3], 1});
-    if (!ctx->loco_M.ensure((nM + (size_t)Kp) * 8) || !ctx->loco_idx.ensure((size_t)npos * 4) ||
-        !ctx->loco_off.ensure((size_t)(ncfg + 1) * 8) || !ctx->loco_list.ensure(std::max<size_t>(ctx->loco_hlist.size(), 1) * 4) ||
-        !ctx->loco_Z.ensure((size_t)npos * (size_t)Jp * 8) || !ctx->loco_aux.ensure((size_t)npos * 3 * 8) ||
-        !ctx->loco_pred.ensure((size_t)m * 8) || !ctx->loco_info.ensure((size_t)ncfg * 4 * 8) ||
-        !ctx->loco_v.ensure((size_t)nvg * (size_t)Jp * 8) || (nblk[3] > 0 && !ctx->loco_H.ensure((size_t)nblk[3] * (size_t)hslice * 8)))
+    UnitPass ps;
+    if ((rc = unit_pass_stage(ctx, "loco", K, J, M, beta, sorted_rows, cfg_offsets, ncfg, fsnap::loco_scratch_doubles, &ps)))
+        return rc;
+    const int nblk3 = ps.bins.nblk[3];
+    if (!ctx->loco_pred.ensure((size_t)m * 8) || !ctx->loco_info.ensure((size_t)ncfg * 4 * 8) ||
+        !ctx->loco_v.ensure((size_t)ps.nvg * (size_t)ps.Jp * 8) ||
+        (nblk3 > 0 && !ctx->loco_H.ensure((size_t)nblk3 * (size_t)ps.hslice * 8)))
         return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(loco) failed");
-    FSNAP_HIP(hipMemcpyAsync(ctx->loco_M.p, ctx->loco_hM.data(), (nM + (size_t)Kp) * 8, hipMemcpyHostToDevice, ctx->stream),
-              "hipMemcpy(M)");
-    FSNAP_HIP(hipMemcpyAsync(ctx->loco_idx.p, sorted_rows, (size_t)npos * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(idx)");
-    FSNAP_HIP(hipMemcpyAsync(ctx->loco_off.p, cfg_offsets, (size_t)(ncfg + 1) * 8, hipMemcpyHostToDevice, ctx->stream),
-              "hipMemcpy(offsets)");
-    if (!ctx->loco_hlist.empty())
-        FSNAP_HIP(hipMemcpyAsync(ctx->loco_list.p, ctx->loco_hlist.data(), ctx->loco_hlist.size() * 4, hipMemcpyHostToDevice,
-                                 ctx->stream),
-                  "hipMemcpy(lists)");
     FSNAP_HIP(hipMemsetAsync(ctx->loco_pred.p, 0xFF, (size_t)m * 8, ctx->stream), "hipMemset(pred)");   // all-ones: NaN
-    double* aux = (double*)ctx->loco_aux.p;
-    FSNAP_HIP(fsnap::launch_loco_zeta(ctx->dA, ctx->lda, (int)K, (const int*)ctx->loco_idx.p, npos, wpack,
-                                      (const double*)ctx->loco_M.p, (int)Jp, (const double*)ctx->loco_M.p + nM,
-                                      (double*)ctx->loco_Z.p, aux, aux + npos, aux + 2 * npos, ctx->stream),
-              "launch fsnap_loco_zeta_k");
-    size_t first = 0;
-    for (int b = 0; b < 4; ++b) {
-        const int ncl = (int)bins.lists[b].size();
-        if (ncl > 0)
-            FSNAP_HIP(fsnap::launch_loco_cfg(bins.D[b], nblk[b], (const double*)ctx->loco_Z.p, (int)Jp, (int)J, aux, aux + npos,
-                                             aux + 2 * npos, (const int*)ctx->loco_idx.p, (const int64_t*)ctx->loco_off.p,
-                                             (const int*)ctx->loco_list.p + first, ncl, (double*)ctx->loco_H.p, (int)dmax,
-                                             (double*)ctx->loco_v.p, (double*)ctx->loco_pred.p, (double*)ctx->loco_info.p,
-                                             ctx->stream),
-                      "launch fsnap_loco_cfg_k");
-        first += (size_t)ncl;
-    }
+    const auto launch = [&](int D, int nblk, size_t first, int ncl) {
+        return fsnap::launch_loco_cfg(D, nblk, ps.Z, ps.Jp, (int)J, ps.pw, ps.pe, ps.pb, ps.idx, ps.off, ps.lists + first, ncl,
+                                      (double*)ctx->loco_H.p, ps.dmax, (double*)ctx->loco_v.p, (double*)ctx->loco_pred.p,
+                                      (double*)ctx->loco_info.p, ctx->stream);
+    };
+    FSNAP_HIP(launch_bins(ps.bins, launch), "launch fsnap_loco_cfg_k");
     ctx->loco_hinfo.resize((size_t)ncfg * 4);
     FSNAP_HIP(hipMemcpyAsync(pred_out, ctx->loco_pred.p, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(pred)");
     FSNAP_HIP(hipMemcpyAsync(ctx->loco_hinfo.data(), ctx->loco_info.p, (size_t)ncfg * 32, hipMemcpyDeviceToHost, ctx->stream),
@@ -2822,16 +2874,9 @@ int fsnap_loco_rows_uq(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, co
     const char* who = "fsnap_loco_rows_uq";
     if (!M || !beta || !cfg_offsets || !pred_out || !lev_out || (ncfg > 0 && !cfg_info_out))
         return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
-    if (K < 1 || K > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: K = %lld", who, (long long)K);
-    if (J < 1 || J > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: J = %lld", who, (long long)J);
-    if (ncfg < 0 || ncfg > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: ncfg = %lld", who, (long long)ncfg);
-    const int64_t m = ctx->m;
-    if (m > 0 && K != ctx->K)
-        return ctx->fail(FSNAP_E_ARG, "%s: K = %lld, the resident rows have %lld columns", who, (long long)K, (long long)ctx->K);
-    if (m > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: needs m < 2^31", who);
-    int rc = check_unit_index(ctx, who, "cfg_offsets", sorted_rows, cfg_offsets, ncfg, m, [](int64_t, int32_t) { return 0; });
+    int rc = unit_pass_check(ctx, who, K, J, sorted_rows, cfg_offsets, ncfg);
     if (rc) return rc;
-    const int64_t npos = cfg_offsets[ncfg];
+    const int64_t m = ctx->m, npos = cfg_offsets[ncfg];
     for (int64_t i = 0; i < m; ++i) pred_out[i] = lev_out[i] = std::numeric_limits<double>::quiet_NaN();
     for (int64_t c = 0; c < ncfg; ++c) {      // empty configurations: nothing to leave out
         cfg_info_out[6 * c] = 0.0;
@@ -2842,63 +2887,22 @@ int fsnap_loco_rows_uq(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, co
         cfg_info_out[6 * c + 5] = 0.0;
     }
     if (npos == 0) return FSNAP_OK;
-    if ((rc = check_rows(ctx)) || (rc = check_weights(ctx))) return rc;
-    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-    if (ctx->uq_inflight) {
-        FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-        ctx->uq_inflight = false;
-    }
-    int npk = 0;
-    if ((rc = ensure_wpack(ctx, &npk))) return rc;
-    const double* wpack = ctx->wpack_override ? ctx->wpack_override : (const double*)ctx->wpack.p;
-    // configurations by solve size d_c = min(n_c, J); general path: one (dmax^2 + 3 dmax) slice of scratch per workgroup
-    const UnitBins bins = bin_units(
-        ncfg, [&](int64_t c) { return cfg_offsets[c + 1] - cfg_offsets[c]; }, J, fsnap::LOCO_MAX_LDS_D, ctx->num_cu,
-        [](int64_t dmax) { return dmax * dmax + 3 * dmax; }, ctx->loco_hlist);
-    const int64_t dmax = bins.dmax, hslice = dmax * dmax + 3 * dmax;
-    const int* nblk = bins.nblk;
-    const int64_t Kp = (K + 15) / 16 * 16, Jp = (J + 15) / 16 * 16;
-    const size_t nM = (size_t)(Kp * Jp);
-    ctx->loco_hM.assign(nM + (size_t)Kp, 0.0);
-    for (int64_t k = 0; k < K; ++k) std::memcpy(&ctx->loco_hM[(size_t)(k * Jp)], M + k * J, (size_t)J * 8);
-    std::memcpy(&ctx->loco_hM[nM], beta, (size_t)K * 8);
-    const int nvg = std::max({nblk[0], nblk[1], nblk[2], nblk[3], 1});
-    if (!ctx->loco_M.ensure((nM + (size_t)Kp) * 8) || !ctx->loco_idx.ensure((size_t)npos * 4) ||
-        !ctx->loco_off.ensure((size_t)(ncfg + 1) * 8) || !ctx->loco_list.ensure(std::max<size_t>(ctx->loco_hlist.size(), 1) * 4) ||
-        !ctx->loco_Z.ensure((size_t)npos * (size_t)Jp * 8) || !ctx->loco_aux.ensure((size_t)npos * 3 * 8) ||
-        !ctx->loco_pred.ensure((size_t)m * 8) || !ctx->loco_lev.ensure((size_t)m * 8) ||
-        !ctx->loco_info.ensure((size_t)ncfg * 6 * 8) ||
-        !ctx->loco_v.ensure((size_t)nvg * (size_t)Jp * 8) || (nblk[3] > 0 && !ctx->loco_H.ensure((size_t)nblk[3] * (size_t)hslice * 8)))
+    UnitPass ps;
+    if ((rc = unit_pass_stage(ctx, "loco", K, J, M, beta, sorted_rows, cfg_offsets, ncfg, fsnap::loco_uq_scratch_doubles, &ps)))
+        return rc;
+    const int nblk3 = ps.bins.nblk[3];
+    if (!ctx->loco_pred.ensure((size_t)m * 8) || !ctx->loco_lev.ensure((size_t)m * 8) ||
+        !ctx->loco_info.ensure((size_t)ncfg * 6 * 8) || !ctx->loco_v.ensure((size_t)ps.nvg * (size_t)ps.Jp * 8) ||
+        (nblk3 > 0 && !ctx->loco_H.ensure((size_t)nblk3 * (size_t)ps.hslice * 8)))
         return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(loco) failed");
-    FSNAP_HIP(hipMemcpyAsync(ctx->loco_M.p, ctx->loco_hM.data(), (nM + (size_t)Kp) * 8, hipMemcpyHostToDevice, ctx->stream),
-              "hipMemcpy(M)");
-    FSNAP_HIP(hipMemcpyAsync(ctx->loco_idx.p, sorted_rows, (size_t)npos * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(idx)");
-    FSNAP_HIP(hipMemcpyAsync(ctx->loco_off.p, cfg_offsets, (size_t)(ncfg + 1) * 8, hipMemcpyHostToDevice, ctx->stream),
-              "hipMemcpy(offsets)");
-    if (!ctx->loco_hlist.empty())
-        FSNAP_HIP(hipMemcpyAsync(ctx->loco_list.p, ctx->loco_hlist.data(), ctx->loco_hlist.size() * 4, hipMemcpyHostToDevice,
-                                 ctx->stream),
-                  "hipMemcpy(lists)");
     FSNAP_HIP(hipMemsetAsync(ctx->loco_pred.p, 0xFF, (size_t)m * 8, ctx->stream), "hipMemset(pred)");   // all-ones: NaN
     FSNAP_HIP(hipMemsetAsync(ctx->loco_lev.p, 0xFF, (size_t)m * 8, ctx->stream), "hipMemset(lev)");
-    double* aux = (double*)ctx->loco_aux.p;
-    FSNAP_HIP(fsnap::launch_loco_zeta(ctx->dA, ctx->lda, (int)K, (const int*)ctx->loco_idx.p, npos, wpack,
-                                      (const double*)ctx->loco_M.p, (int)Jp, (const double*)ctx->loco_M.p + nM,
-                                      (double*)ctx->loco_Z.p, aux, aux + npos, aux + 2 * npos, ctx->stream),
-              "launch fsnap_loco_zeta_k");
-    size_t first = 0;
-    for (int b = 0; b < 4; ++b) {
-        const int ncl = (int)bins.lists[b].size();
-        if (ncl > 0)
-            FSNAP_HIP(fsnap::launch_loco_uq_cfg(bins.D[b], nblk[b], (const double*)ctx->loco_Z.p, (int)Jp, (int)J, aux,
-                                                aux + npos, aux + 2 * npos, (const int*)ctx->loco_idx.p,
-                                                (const int64_t*)ctx->loco_off.p, (const int*)ctx->loco_list.p + first, ncl,
-                                                (double*)ctx->loco_H.p, (int)dmax, (double*)ctx->loco_v.p,
-                                                (double*)ctx->loco_pred.p, (double*)ctx->loco_lev.p,
-                                                (double*)ctx->loco_info.p, ctx->stream),
-                      "launch fsnap_loco_uq_cfg_k");
-        first += (size_t)ncl;
-    }
+    const auto launch = [&](int D, int nblk, size_t first, int ncl) {
+        return fsnap::launch_loco_uq_cfg(D, nblk, ps.Z, ps.Jp, (int)J, ps.pw, ps.pe, ps.pb, ps.idx, ps.off, ps.lists + first, ncl,
+                                         (double*)ctx->loco_H.p, ps.dmax, (double*)ctx->loco_v.p, (double*)ctx->loco_pred.p,
+                                         (double*)ctx->loco_lev.p, (double*)ctx->loco_info.p, ctx->stream);
+    };
+    FSNAP_HIP(launch_bins(ps.bins, launch), "launch fsnap_loco_uq_cfg_k");
     ctx->loco_hinfo.resize((size_t)ncfg * 6);
     FSNAP_HIP(hipMemcpyAsync(pred_out, ctx->loco_pred.p, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(pred)");
     FSNAP_HIP(hipMemcpyAsync(lev_out, ctx->loco_lev.p, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(lev)");
@@ -2924,16 +2928,9 @@ int fsnap_influence_rows(fsnap_ctx* ctx, int mode, int64_t K, int64_t J, const d
         return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
     if (!full && (V_out || Wv_out || pred_out))
         return ctx->fail(FSNAP_E_ARG, "%s: V_out, Wv_out and pred_out need FSNAP_INFL_FULL", who);
-    if (K < 1 || K > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: K = %lld", who, (long long)K);
-    if (J < 1 || J > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: J = %lld", who, (long long)J);
-    if (ncfg < 0 || ncfg > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: ncfg = %lld", who, (long long)ncfg);
-    const int64_t m = ctx->m;
-    if (m > 0 && K != ctx->K)
-        return ctx->fail(FSNAP_E_ARG, "%s: K = %lld, the resident rows have %lld columns", who, (long long)K, (long long)ctx->K);
-    if (m > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: needs m < 2^31", who);
-    int rc = check_unit_index(ctx, who, "cfg_offsets", sorted_rows, cfg_offsets, ncfg, m, [](int64_t, int32_t) { return 0; });
+    int rc = unit_pass_check(ctx, who, K, J, sorted_rows, cfg_offsets, ncfg);
     if (rc) return rc;
-    const int64_t npos = cfg_offsets[ncfg];
+    const int64_t m = ctx->m, npos = cfg_offsets[ncfg];
     if (Ws_out) std::fill(Ws_out, Ws_out + J * J, 0.0);
     if (Wv_out) std::fill(Wv_out, Wv_out + J * J, 0.0);
     if (ncfg == 0 || m == 0) return FSNAP_OK;
@@ -2950,81 +2947,42 @@ int fsnap_influence_rows(fsnap_ctx* ctx, int mode, int64_t K, int64_t J, const d
     if (S_out) std::fill(S_out, S_out + ncfg * J, 0.0);
     if (V_out) std::fill(V_out, V_out + ncfg * J, 0.0);
     if (npos == 0) return FSNAP_OK;
-    if ((rc = check_rows(ctx)) || (rc = check_weights(ctx))) return rc;
-    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-    if (ctx->uq_inflight) {
-        FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-        ctx->uq_inflight = false;
-    }
-    int npk = 0;
-    if ((rc = ensure_wpack(ctx, &npk))) return rc;
-    const double* wpack = ctx->wpack_override ? ctx->wpack_override : (const double*)ctx->wpack.p;
-    // configurations by solve size d_c = min(n_c, J) as fsnap_loco_rows_uq bins them (kernel I1 runs the body with UQ = true)
-    const UnitBins bins = bin_units(
-        ncfg, [&](int64_t c) { return cfg_offsets[c + 1] - cfg_offsets[c]; }, J, fsnap::LOCO_MAX_LDS_D, ctx->num_cu,
-        [](int64_t dmax) { return dmax * dmax + 3 * dmax; }, ctx->loco_hlist);
-    const int64_t dmax = bins.dmax, hslice = dmax * dmax + 3 * dmax;
-    const int* nblk = bins.nblk;
-    const int64_t Kp = (K + 15) / 16 * 16, Jp = (J + 15) / 16 * 16;
-    const size_t nM = (size_t)(Kp * Jp);
-    ctx->loco_hM.assign(nM + (size_t)Kp, 0.0);
-    for (int64_t k = 0; k < K; ++k) std::memcpy(&ctx->loco_hM[(size_t)(k * Jp)], M + k * J, (size_t)J * 8);
-    std::memcpy(&ctx->loco_hM[nM], beta, (size_t)K * 8);
-    const int nvg = std::max({nblk[0], nblk[1], nblk[2], nblk[3], 1});
-    const int64_t ntiles = (Jp / 16) * (Jp / 16 + 1) / 2;
+    const int64_t Jp = (J + 15) / 16 * 16, ntiles = (Jp / 16) * (Jp / 16 + 1) / 2;
     const bool want_ws = Ws_out != nullptr, want_wv = Wv_out != nullptr;
     if ((want_ws || want_wv) && fsnap::infl_chunks(ncfg) * ntiles > 0x7FFFFFFF)
         return ctx->fail(FSNAP_E_ARG, "%s: %lld units x %lld tiles are too many for one launch", who, (long long)ncfg, (long long)ntiles);
+    // the bins and scratch of fsnap_loco_rows_uq (kernel I1 runs the body with UQ = true)
+    UnitPass ps;
+    if ((rc = unit_pass_stage(ctx, "influence", K, J, M, beta, sorted_rows, cfg_offsets, ncfg, fsnap::loco_uq_scratch_doubles, &ps)))
+        return rc;
+    const int nblk3 = ps.bins.nblk[3];
     const size_t nUJ = (size_t)ncfg * (size_t)Jp;
-    if (!ctx->loco_M.ensure((nM + (size_t)Kp) * 8) || !ctx->loco_idx.ensure((size_t)npos * 4) ||
-        !ctx->loco_off.ensure((size_t)(ncfg + 1) * 8) || !ctx->loco_list.ensure(std::max<size_t>(ctx->loco_hlist.size(), 1) * 4) ||
-        !ctx->loco_Z.ensure((size_t)npos * (size_t)Jp * 8) || !ctx->loco_aux.ensure((size_t)npos * 3 * 8) ||
-        !ctx->infl_S.ensure(nUJ * 8) || !ctx->infl_unit.ensure((size_t)ncfg * 3 * 8) ||
+    if (!ctx->infl_S.ensure(nUJ * 8) || !ctx->infl_unit.ensure((size_t)ncfg * 3 * 8) ||
         ((want_ws || want_wv) && (!ctx->infl_part.ensure((size_t)(fsnap::infl_chunks(ncfg) * ntiles) * 256 * 8) ||
                                   !ctx->infl_W.ensure((size_t)(2 * J * J) * 8))) ||
         (full && (!ctx->loco_pred.ensure((size_t)m * 8) || !ctx->loco_info.ensure((size_t)ncfg * 4 * 8) ||
-                  !ctx->infl_V.ensure(nUJ * 8) || !ctx->loco_v.ensure((size_t)nvg * (size_t)Jp * 8) ||
-                  (nblk[3] > 0 && !ctx->loco_H.ensure((size_t)nblk[3] * (size_t)hslice * 8)))))
+                  !ctx->infl_V.ensure(nUJ * 8) || !ctx->loco_v.ensure((size_t)ps.nvg * (size_t)Jp * 8) ||
+                  (nblk3 > 0 && !ctx->loco_H.ensure((size_t)nblk3 * (size_t)ps.hslice * 8)))))
         return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(influence) failed");
-    FSNAP_HIP(hipMemcpyAsync(ctx->loco_M.p, ctx->loco_hM.data(), (nM + (size_t)Kp) * 8, hipMemcpyHostToDevice, ctx->stream),
-              "hipMemcpy(M)");
-    FSNAP_HIP(hipMemcpyAsync(ctx->loco_idx.p, sorted_rows, (size_t)npos * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(idx)");
-    FSNAP_HIP(hipMemcpyAsync(ctx->loco_off.p, cfg_offsets, (size_t)(ncfg + 1) * 8, hipMemcpyHostToDevice, ctx->stream),
-              "hipMemcpy(offsets)");
-    FSNAP_HIP(hipMemcpyAsync(ctx->loco_list.p, ctx->loco_hlist.data(), ctx->loco_hlist.size() * 4, hipMemcpyHostToDevice,
-                             ctx->stream),
-              "hipMemcpy(lists)");
     // configurations without rows are in no list: their rows of S and V stay zero for kernel I2
     FSNAP_HIP(hipMemsetAsync(ctx->infl_S.p, 0, nUJ * 8, ctx->stream), "hipMemset(S)");
     if (full) {
         FSNAP_HIP(hipMemsetAsync(ctx->infl_V.p, 0, nUJ * 8, ctx->stream), "hipMemset(V)");
         FSNAP_HIP(hipMemsetAsync(ctx->loco_pred.p, 0xFF, (size_t)m * 8, ctx->stream), "hipMemset(pred)");   // all-ones: NaN
     }
-    double* aux = (double*)ctx->loco_aux.p;
-    FSNAP_HIP(fsnap::launch_loco_zeta(ctx->dA, ctx->lda, (int)K, (const int*)ctx->loco_idx.p, npos, wpack,
-                                      (const double*)ctx->loco_M.p, (int)Jp, (const double*)ctx->loco_M.p + nM,
-                                      (double*)ctx->loco_Z.p, aux, aux + npos, aux + 2 * npos, ctx->stream),
-              "launch fsnap_loco_zeta_k");
     if (full) {
-        size_t first = 0;
-        for (int b = 0; b < 4; ++b) {
-            const int ncl = (int)bins.lists[b].size();
-            if (ncl > 0)
-                FSNAP_HIP(fsnap::launch_infl_cfg(bins.D[b], nblk[b], (const double*)ctx->loco_Z.p, (int)Jp, (int)J, aux,
-                                                 aux + npos, aux + 2 * npos, (const int*)ctx->loco_idx.p,
-                                                 (const int64_t*)ctx->loco_off.p, (const int*)ctx->loco_list.p + first, ncl,
-                                                 (double*)ctx->loco_H.p, (int)dmax, (double*)ctx->loco_v.p,
-                                                 (double*)ctx->loco_pred.p, (double*)ctx->loco_info.p, (double*)ctx->infl_V.p,
-                                                 (double*)ctx->infl_S.p, (double*)ctx->infl_unit.p, ctx->stream),
-                          "launch fsnap_infl_cfg_k");
-            first += (size_t)ncl;
-        }
+        const auto launch = [&](int D, int nblk, size_t first, int ncl) {
+            return fsnap::launch_infl_cfg(D, nblk, ps.Z, ps.Jp, (int)J, ps.pw, ps.pe, ps.pb, ps.idx, ps.off, ps.lists + first, ncl,
+                                          (double*)ctx->loco_H.p, ps.dmax, (double*)ctx->loco_v.p, (double*)ctx->loco_pred.p,
+                                          (double*)ctx->loco_info.p, (double*)ctx->infl_V.p, (double*)ctx->infl_S.p,
+                                          (double*)ctx->infl_unit.p, ctx->stream);
+        };
+        FSNAP_HIP(launch_bins(ps.bins, launch), "launch fsnap_infl_cfg_k");
     } else {
         const int ncl = (int)ctx->loco_hlist.size();      // the four lists one after the other: every configuration with rows
-        FSNAP_HIP(fsnap::launch_infl_scores(std::min(ncl, std::max(1, 16 * ctx->num_cu)), (const double*)ctx->loco_Z.p, (int)Jp,
-                                            (int)J, aux, aux + npos, (const int64_t*)ctx->loco_off.p,
-                                            (const int*)ctx->loco_list.p, ncl, (double*)ctx->infl_S.p,
-                                            (double*)ctx->infl_unit.p, ctx->stream),
+        FSNAP_HIP(fsnap::launch_infl_scores(std::min(ncl, std::max(1, 16 * ctx->num_cu)), ps.Z, ps.Jp, (int)J, ps.pw, ps.pe,
+                                            ps.off, ps.lists, ncl, (double*)ctx->infl_S.p, (double*)ctx->infl_unit.p,
+                                            ctx->stream),
                   "launch fsnap_infl_scores_k");
     }
     double* dW = (double*)ctx->infl_W.p;
@@ -3109,14 +3067,8 @@ int fsnap_ridge_path(fsnap_ctx* ctx, int64_t K, const double* G, const double* c
         return FSNAP_OK;
     }
     if ((rc = check_rows(ctx)) || (rc = check_weights(ctx))) return rc;
-    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-    if (ctx->uq_inflight) {
-        FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-        ctx->uq_inflight = false;
-    }
-    int npk = 0;
-    if ((rc = ensure_wpack(ctx, &npk))) return rc;
-    const double* wpack = ctx->wpack_override ? ctx->wpack_override : (const double*)ctx->wpack.p;
+    const double* wpack = nullptr;
+    if ((rc = resident_weights(ctx, &wpack))) return rc;
     const int nblocks = (int)std::min<int64_t>(nunits, (int64_t)fsnap::path_blocks_per_cu((int)K) * std::max(1, ctx->num_cu));
     const size_t nin = (size_t)(K * K + K + Q);
     if (!ctx->path_in.ensure(nin * 8) || !ctx->path_cls.ensure((size_t)m) || !ctx->loco_idx.ensure((size_t)npos * 4) ||
@@ -3411,8 +3363,8 @@ int fsnap_joint_score(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, int
     const UnitBins bins = bin_units(
         nunits,
         [&](int64_t u) { return ctx->joint_halive[(size_t)u] ? ctx->joint_hoff[(size_t)u + 1] - ctx->joint_hoff[(size_t)u] : 0; }, J,
-        fsnap::JOINT_MAX_LDS_D, ctx->num_cu, [](int64_t dmax) { return dmax * dmax + dmax + fsnap::joint_yslice(dmax); },
-        ctx->joint_hlist);
+        fsnap::JOINT_MAX_LDS_D, ctx->num_cu,
+        [](int64_t dmax) { return fsnap::loco_scratch_doubles(dmax) + fsnap::joint_yslice(dmax); }, ctx->joint_hlist);
     const int64_t dmax = bins.dmax;
     const int* nblk = bins.nblk;
     if (ctx->joint_hlist.empty() || npos == 0) return FSNAP_OK;
@@ -3432,7 +3384,7 @@ int fsnap_joint_score(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, int
     }
     ctx->joint_hB.assign((size_t)std::max<int64_t>(Jp * rp, 1), 0.0);
     for (int64_t j = 0; j < J && r > 0; ++j) std::memcpy(&ctx->joint_hB[(size_t)(j * rp)], B + j * r, (size_t)r * 8);
-    const int64_t sslice = dmax * dmax + dmax, yslice = fsnap::joint_yslice(dmax);
+    const int64_t sslice = fsnap::loco_scratch_doubles(dmax), yslice = fsnap::joint_yslice(dmax);
     if (!ctx->joint_F.ensure((size_t)(Kp * Wp) * 8) || !ctx->joint_B.ensure(ctx->joint_hB.size() * 8) ||
         !ctx->joint_ZP.ensure((size_t)npos * (size_t)Wp * 8) || !ctx->joint_list.ensure(ctx->joint_hlist.size() * 4) ||
         !ctx->joint_out.ensure((size_t)nunits * 2 * 8) || !ctx->joint_info.ensure((size_t)nunits * 4 * 8) ||
@@ -3447,18 +3399,13 @@ int fsnap_joint_score(fsnap_ctx* ctx, int64_t K, int64_t J, const double* M, int
     FSNAP_HIP(fsnap::launch_joint_rows(ctx->dA, ctx->lda, (int)K, (const int*)ctx->joint_idx.p, npos, (const double*)ctx->joint_om.p,
                                        (const double*)ctx->joint_F.p, (int)Wp, (double*)ctx->joint_ZP.p, ctx->stream),
               "launch fsnap_joint_rows_k");
-    size_t first = 0;
-    for (int b = 0; b < 4; ++b) {
-        const int ncl = (int)bins.lists[b].size();
-        if (ncl > 0)
-            FSNAP_HIP(fsnap::launch_joint_units(bins.D[b], nblk[b], (const double*)ctx->joint_ZP.p, (int)Wp, (int)Jp, (int)J, (int)rp,
-                                                (const double*)ctx->joint_B.p, tau, (const int64_t*)ctx->joint_off.p,
-                                                (const int*)ctx->joint_list.p + first, ncl, (double*)ctx->joint_S.p, (int)dmax,
-                                                (double*)ctx->joint_Y.p, (double*)ctx->joint_out.p, (double*)ctx->joint_info.p,
-                                                ctx->stream),
-                      "launch fsnap_joint_unit_k");
-        first += (size_t)ncl;
-    }
+    const auto launch = [&](int D, int nwg, size_t first, int ncl) {
+        return fsnap::launch_joint_units(D, nwg, (const double*)ctx->joint_ZP.p, (int)Wp, (int)Jp, (int)J, (int)rp,
+                                         (const double*)ctx->joint_B.p, tau, (const int64_t*)ctx->joint_off.p,
+                                         (const int*)ctx->joint_list.p + first, ncl, (double*)ctx->joint_S.p, (int)dmax,
+                                         (double*)ctx->joint_Y.p, (double*)ctx->joint_out.p, (double*)ctx->joint_info.p, ctx->stream);
+    };
+    FSNAP_HIP(launch_bins(bins, launch), "launch fsnap_joint_unit_k");
     ctx->joint_hout.resize((size_t)nunits * 2);
     ctx->joint_hinfo.resize((size_t)nunits * 4);
     FSNAP_HIP(hipMemcpyAsync(ctx->joint_hout.data(), ctx->joint_out.p, (size_t)nunits * 16, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(out)");

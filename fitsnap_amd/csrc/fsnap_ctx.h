@@ -134,15 +134,18 @@ struct fsnap_ctx {
     bool sel_active = false, sel_has_scale = false;
     int sel_ncat = 0, sel_objective = 0;
     int64_t sel_m = 0, sel_nch = 0;
-    // fsnap_loco_rows: [padded M | padded beta], sorted row index, configuration offsets and per-bin lists, zeta per position
-    // (npos x Jp), (w, e, a . beta) per position, per-row predictions, per-configuration info, per-workgroup scratch (v; H of
-    // the configurations too large for LDS); kept between calls like the other workspaces
-    DevBuf loco_M, loco_idx, loco_off, loco_list, loco_Z, loco_aux, loco_pred, loco_info, loco_v, loco_H;
-    DevBuf loco_lev;                   // fsnap_loco_rows_uq: the leverage per row (its other buffers are those above)
-    std::vector<double> loco_hM, loco_hinfo;
+    // fsnap_loco_rows / _uq / fsnap_influence_rows, kept between calls like the other workspaces.  Sized and filled by their
+    // shared stage (unit_pass_stage in fsnap_capi.cpp): [padded M | padded beta] and its host staging, sorted row index,
+    // configuration offsets, per-bin lists and their host copy, zeta per position (npos x Jp), (w, e, a . beta) per position
+    DevBuf loco_M, loco_idx, loco_off, loco_list, loco_Z, loco_aux;
+    std::vector<double> loco_hM;
     std::vector<int32_t> loco_hlist;
-    // fsnap_influence_rows: V and S (ncfg x Jp each), the unit records (ncfg x 3), kernel I2's chunk partials and [W_s | W_v]
-    // (its other buffers are fsnap_loco_rows'); kept between calls
+    // sized by the entry point that uses them: per-row predictions and leverages (_uq), per-configuration info (4 or 6 columns)
+    // and the host copy it is read back into, per-workgroup scratch (v; H of the configurations too large for LDS)
+    DevBuf loco_pred, loco_lev, loco_info, loco_v, loco_H;
+    std::vector<double> loco_hinfo;
+    // fsnap_influence_rows' own: V and S (ncfg x Jp each), the unit records (ncfg x 3), kernel I2's chunk partials and
+    // [W_s | W_v]; kept between calls
     DevBuf infl_V, infl_S, infl_unit, infl_part, infl_W;
     // fsnap_ridge_path: [G | c | alphas], row classes, per-workgroup base tiles, sums, info, predictions (the unit index and
     // offsets share loco_idx / loco_off); kept between calls

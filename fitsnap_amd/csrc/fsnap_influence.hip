@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void fsnap_infl_cfg_k(const double* __restrict
                          vbuf, pred, info + 4 * (int64_t)c, V + (int64_t)c * Jp, S + (int64_t)c * Jp, unit + 3 * (int64_t)c);
         }
     } else {
-        double* H = Hg + (int64_t)blockIdx.x * ((int64_t)dmax * dmax + 3 * (int64_t)dmax);
+        double* H = Hg + (int64_t)blockIdx.x * fsnap::loco_uq_scratch_doubles(dmax);
         double* r = H + (int64_t)dmax * dmax;
         for (int q = blockIdx.x; q < ncl; q += gridDim.x) {
             const int c = clist[q];

@@ -305,7 +305,7 @@ __global__ __launch_bounds__(256) void fsnap_joint_unit_k(const double* __restri
                                    out + 2 * (int64_t)u, info + 4 * (int64_t)u);
         }
     } else {
-        double* H = Sg + (int64_t)blockIdx.x * ((int64_t)dmax * dmax + dmax);
+        double* H = Sg + (int64_t)blockIdx.x * fsnap::loco_scratch_doubles(dmax);
         double* lg = H + (int64_t)dmax * dmax;
         const int ntmax = (dmax + 15) / 16;
         double* yg = Yg + (int64_t)blockIdx.x * fsnap::joint_yslice(dmax);

@@ -228,18 +228,22 @@ hipError_t launch_loco_zeta(const double* A, int64_t lda, int K, const int* idx,
                             const double* Mp, int Jp, const double* bp, double* Z, double* pw, double* pe, double* pb,
                             hipStream_t st);
 // Kernel L2 over the configurations clist[ncl] (positions off[c] .. off[c + 1]); D = 32 / 64 / 128: d_c = min(n_c, J) <= D,
-// H in LDS; D = 0: any d_c <= dmax, H in Hg (nblocks x (dmax^2 + dmax) doubles).  vg: nblocks x Jp doubles of scratch.
+// H in LDS; D = 0: any d_c <= dmax, H in Hg (nblocks x loco_scratch_doubles(dmax)).  vg: nblocks x Jp doubles of scratch.
 // pred[idx[p]] = LOO prediction (NaN for a configuration that is not identifiable); info[4 c ..] = (d_c, smallest pivot,
 // identifiable, n space).
 constexpr int LOCO_MAX_LDS_D = 128;
 constexpr double LOCO_PIVOT_TOL = 1e-10;     // pivots of I - S_c (diagonal <= 1) at or below this: not identifiable
+// One workgroup's slice of Hg (D = 0), in doubles, for the host that sizes Hg and the kernel that indexes it: H (dmax x dmax)
+// and one dmax-vector (kernels L2 and J2), or three (kernels L3 and I1)
+constexpr int64_t loco_scratch_doubles(int64_t dmax) { return dmax * dmax + dmax; }
+constexpr int64_t loco_uq_scratch_doubles(int64_t dmax) { return dmax * dmax + 3 * dmax; }
 hipError_t launch_loco_cfg(int D, int nblocks, const double* Z, int Jp, int J, const double* pw, const double* pe,
                            const double* pb, const int* idx, const int64_t* off, const int* clist, int ncl, double* Hg,
                            int dmax, double* vg, double* pred, double* info, hipStream_t st);
 // Kernel L3 (fsnap_loco_uq.hip): launch_loco_cfg's geometry and predictions (bit for bit), plus lev[idx[p]] = the leave-out
 // leverage q_i of every row (NaN for a configuration that is not identifiable) and info[6 c ..] = (d_c, smallest pivot,
 // identifiable, n space, log det H_c, e_c^T H_c^-1 e_c; the last two NaN when not identifiable).  D = 0: Hg holds
-// nblocks x (dmax^2 + 3 dmax) doubles.
+// nblocks x loco_uq_scratch_doubles(dmax).
 hipError_t launch_loco_uq_cfg(int D, int nblocks, const double* Z, int Jp, int J, const double* pw, const double* pe,
                               const double* pb, const int* idx, const int64_t* off, const int* clist, int ncl, double* Hg,
                               int dmax, double* vg, double* pred, double* lev, double* info, hipStream_t st);
@@ -247,7 +251,7 @@ hipError_t launch_loco_uq_cfg(int D, int nblocks, const double* Z, int Jp, int J
 // Influence vectors and outer-product sums (fsnap_influence.hip).  Kernel I1: launch_loco_cfg's geometry, predictions and info
 // (bit for bit), plus per unit c of the list V[c Jp ..] = v_c (zeros when not identifiable), S[c Jp ..] = s_c = Z_c^T e_c and
 // unit[3 c ..] = (|v_c|^2, |s_c|^2, s_c . v_c) (first and third NaN when not identifiable); columns J ... Jp - 1 of V and S are
-// written as zeros.  D = 0: Hg holds nblocks x (dmax^2 + 3 dmax) doubles.
+// written as zeros.  D = 0: Hg holds nblocks x loco_uq_scratch_doubles(dmax).
 hipError_t launch_infl_cfg(int D, int nblocks, const double* Z, int Jp, int J, const double* pw, const double* pe,
                            const double* pb, const int* idx, const int64_t* off, const int* clist, int ncl, double* Hg,
                            int dmax, double* vg, double* pred, double* info, double* V, double* S, double* unit,
@@ -332,7 +336,7 @@ hipError_t launch_cv_rows(const double* A, int64_t lda, const double* b, const d
 hipError_t launch_joint_rows(const double* A, int64_t lda, int K, const int* idx, int64_t npos, const double* om,
                              const double* Fp, int Wp, double* ZP, hipStream_t st);
 // Kernel J2 for the ncl units of ulist (D = 32 / 64 / 128: S in LDS for dim S = min(n_u, J) <= D; D = 0: S in a slice of
-// dmax * dmax doubles of Sg per workgroup, the right-hand-side fragments in JOINT_YSLICE(dmax) doubles of Yg per workgroup):
+// loco_scratch_doubles(dmax) of Sg per workgroup, the right-hand-side fragments in joint_yslice(dmax) doubles of Yg per workgroup):
 // S = I + Z Z^T / tau (n_u <= J) or I + Z^T Z / tau = L L^T; out[2 u] = gain = sum log L_ii; out[2 u + 1] = reduction (only
 // with rp > 0) = ||L^-1 Pi||_F^2 / tau (n space; Pi = columns [Jp, Jp + rp) of ZP) or ||B||_F^2 - ||L^-1 B||_F^2 (J space; Bp:
 // device, Jp x rp row-major, zero-padded); info[4 u ..] = (dim S, n space 1 / 0, smallest pivot, n_u).

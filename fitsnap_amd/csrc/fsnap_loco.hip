@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) void fsnap_loco_cfg_k(const double* __restrict
                                 info + 4 * (int64_t)c);
         }
     } else {
-        double* H = Hg + (int64_t)blockIdx.x * ((int64_t)dmax * dmax + dmax);
+        double* H = Hg + (int64_t)blockIdx.x * fsnap::loco_scratch_doubles(dmax);
         double* r = H + (int64_t)dmax * dmax;
         for (int q = blockIdx.x; q < ncl; q += gridDim.x) {
             const int c = clist[q];

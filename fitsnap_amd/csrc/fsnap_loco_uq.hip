@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void fsnap_loco_uq_cfg_k(const double* __restr
                             spart, vbuf, pred, lev, info + 6 * (int64_t)c);
         }
     } else {
-        double* H = Hg + (int64_t)blockIdx.x * ((int64_t)dmax * dmax + 3 * (int64_t)dmax);
+        double* H = Hg + (int64_t)blockIdx.x * fsnap::loco_uq_scratch_doubles(dmax);
         double* r = H + (int64_t)dmax * dmax;
         for (int q = blockIdx.x; q < ncl; q += gridDim.x) {
             const int c = clist[q];

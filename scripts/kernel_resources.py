@@ -34,7 +34,7 @@ def main():
         dem = re.sub(r"\(.*", "", dem.replace("(anonymous namespace)::", ""))
         if flt and flt not in dem:
             continue
-        print(f"{dem:60s} VGPR {r.get('VGPRs', -1):4d} AGPR {r.get('AGPRs', -1):4d} SGPR {r.get('SGPRs', -1):4d} "
+        print(f"{dem:60s} VGPR {r.get('VGPRs', -1):4d} AGPR {r.get('AGPRs', -1):4d} SGPR {r.get('TotalSGPRs', r.get('SGPRs', -1)):4d} "
               f"spill V {r.get('VGPRs Spill', -1)} S {r.get('SGPRs Spill', -1)} scratch {r.get('ScratchSize [bytes/lane]', -1)} "
               f"LDS {r.get('LDS Size [bytes/block]', -1)} occ {r.get('Occupancy [waves/SIMD]', -1)}")
 

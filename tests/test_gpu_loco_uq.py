@@ -2,8 +2,8 @@
 Solver.loco_predictive) against long-double refits (tests/loco_uq_cases.py) under a-priori rounding bars and an RMS
 comparison with loco_uq_host: a sweep of K, J (J = K and J < K factors) and unit sizes on every tile and bin edge, the
 predictions bit for bit those of fsnap_loco_rows, the layout and edge cases (empty units, unlisted and zero-weight rows, a
-unit that is not identifiable, shuffled units and subsets, repeats, argument errors), the solver method against its host
-route, and two ranks."""
+unit that is not identifiable, shuffled units and subsets, repeats, argument errors), the three entry points that share one
+staging front on one context in both orders, the solver method against its host route, and two ranks."""
 import os
 import subprocess
 import sys
@@ -145,6 +145,44 @@ def test_layout_and_edge_cases(J):
             bq, bd, bl = uc.uq_bars(A[r], b[r], w[r], M, beta, mid["lam_min"], mid["d"], w[r] * (b[r] - hpred[r]), hinfo[u, 4])
             assert np.all(np.abs(lev[r] - hlev[r]) <= 2 * bq), (alpha, u)              # two float64 routes: each within its bar
             assert abs(info[u, 5] - hinfo[u, 5]) <= 2 * bd and abs(info[u, 4] - hinfo[u, 4]) <= 2 * bl, (alpha, u)
+
+
+@pytest.mark.gpu
+def test_entry_points_share_buffers_and_leave_no_state():
+    """fsnap_loco_rows, fsnap_loco_rows_uq and fsnap_influence_rows (FULL) on one context, in that order and then in the
+    reverse order, at K = J = 144 with one unit in each bin (8, 40, 100 rows: the LDS classes 32, 64, 128; 140 rows: global
+    scratch, dmax = 140, whose slice differs between the first and the other two).  They stage the same buffers: the
+    predictions and the first four info columns have the same bits from all three and in both orders, and so has everything
+    else an entry point returns (leverages, unit records, vectors, sums) between the two orders."""
+    K, alpha, sizes = 144, 1e-4, [8, 40, 100, 140]
+    A, b, w, _ = lc.config_rows(33, K, sizes)
+    Aw, bw = A * w[:, None], b * w
+    G, c = Aw.T @ Aw, Aw.T @ bw
+    M = loco.factor_cholesky(G, alpha)
+    beta = np.linalg.solve(G + alpha * np.eye(K), c)
+    rows = np.arange(len(b), dtype=np.int32)
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    calls = {
+        "loco": lambda ctx: dict(zip(("pred", "info"), ctx.loco_rows(M, beta, rows, off))),
+        "uq": lambda ctx: dict(zip(("pred", "lev", "info"), ctx.loco_rows_uq(M, beta, rows, off))),
+        "infl": lambda ctx: ctx.influence_rows(M, beta, rows, off, mode=_capi.INFL_FULL),
+    }
+    ctx = upload(A, b, w)
+    try:
+        forward = {name: calls[name](ctx) for name in ("loco", "uq", "infl")}
+        backward = {name: calls[name](ctx) for name in ("infl", "uq", "loco")}
+    finally:
+        ctx.close()
+    ref = forward["loco"]
+    assert ref["info"][:, 0].tolist() == sizes and np.all(ref["info"][:, 2] == 1.0)      # d_c = n_c: one unit per bin
+    assert np.all(np.isfinite(ref["pred"]))
+    for order in (forward, backward):
+        for name, out in order.items():
+            assert same_bits(out["pred"], ref["pred"]) and same_bits(out["info"][:, :4], ref["info"]), name
+    assert np.all(np.isfinite(forward["uq"]["lev"])) and np.all(np.isfinite(forward["infl"]["unit"]))
+    for name, out in forward.items():
+        for key, x in out.items():
+            assert same_bits(x, backward[name][key]), (name, key)
 
 
 @pytest.mark.gpu
