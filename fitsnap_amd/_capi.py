@@ -35,6 +35,8 @@ SELECT_OBJECTIVES = {"sum": SELECT_SUM, "max": SELECT_MAX, "mean": SELECT_MEAN}
 INFL_SCORES, INFL_FULL = 0, 1                   # fsnap_influence_rows: mode
 ROBUST_HUBER, ROBUST_BISQUARE, ROBUST_CAUCHY = 0, 1, 2   # fsnap_robust_reweight: loss
 ROBUST_LOSSES = {"huber": ROBUST_HUBER, "bisquare": ROBUST_BISQUARE, "cauchy": ROBUST_CAUCHY}
+OMP_OMP, OMP_OLS = 0, 1                         # fsnap_omp_gram / fsnap_omp_path: criterion
+OMP_CRITERIA = {"omp": OMP_OMP, "ols": OMP_OLS}
 ROBUST_MAX_CLASSES = 32
 MERR_METHODS = {"iid": MERR_IID, "abc": MERR_ABC, "full": MERR_FULL}
 
@@ -77,6 +79,8 @@ SIGNATURES = {
     "fsnap_cond_info": (c_int, [c_void_p]),
     "fsnap_lasso_gram": (c_int, [c_int64, c_void_p, c_void_p, c_double, c_double, c_int64, c_double, c_void_p,
                                  POINTER(c_int64), POINTER(c_double)]),
+    "fsnap_omp_gram": (c_int, [c_int64, c_void_p, c_void_p, c_double, c_void_p, c_int, c_void_p, c_int64, c_int64, c_void_p,
+                               c_void_p, c_void_p]),
     "fsnap_normal_eq_accumulate": (c_int, [c_void_p, c_void_p]),
     "fsnap_assemble_accumulate": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int,
@@ -141,6 +145,8 @@ SIGNATURES = {
                                  c_void_p, c_void_p]),
     "fsnap_ard_path": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_double, c_void_p,
                                c_void_p, c_void_p, c_void_p]),
+    "fsnap_omp_path": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int64, c_int64, c_void_p,
+                               c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fsnap_select_begin": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int]),
     "fsnap_select_pick": (c_int, [c_void_p, c_int, POINTER(ctypes.c_int32), POINTER(c_double)]),
     "fsnap_select_retire": (c_int, [c_void_p, ctypes.c_int32]),
@@ -298,6 +304,40 @@ def lasso_gram(Q: np.ndarray, q: np.ndarray, y_norm2: float, l1_reg: float, max_
                               byref(nit), byref(gap))
     raise_status(rc, "")
     return w, int(nit.value), float(gap.value)
+
+
+def omp_criterion(criterion) -> int:
+    """The criterion code of "omp" / "ols" (or of a code already); ValueError for anything else."""
+    if isinstance(criterion, str) and criterion.lower() in OMP_CRITERIA:
+        return OMP_CRITERIA[criterion.lower()]
+    if not isinstance(criterion, (str, bool)) and criterion in (OMP_OMP, OMP_OLS):
+        return int(criterion)
+    raise ValueError(f"criterion must be one of {', '.join(OMP_CRITERIA)}, not {criterion!r}")
+
+
+def omp_gram(Q: np.ndarray, q: np.ndarray, y2: float, steps: int, criterion="ols", forced=(), diag_ref=None):
+    """Greedy forward selection on the statistics (fsnap_omp_gram; host side, no GPU needed): ``steps`` steps of orthogonal
+    matching pursuit ("omp") or orthogonal least squares ("ols") after the ``forced`` columns.  ``diag_ref``: the diagonal the
+    dead-column rule compares Q's with (None: Q's own).  Returns (order (steps, int32; -1 once the path has ended), path
+    (steps x 3: e_s, score, pivot), coef (steps x K: the least-squares coefficients on the support of every step))."""
+    lib = load_library()
+    Q = _f64(Q, "Q")
+    q = _f64(q, "q")
+    K = q.shape[0]
+    if Q.shape != (K, K):
+        raise ValueError("Q must be K x K")
+    ref = None if diag_ref is None else _f64(diag_ref, "diag_ref")
+    if ref is not None and ref.shape != (K,):
+        raise ValueError("diag_ref must have K entries")
+    forced = np.ascontiguousarray(np.asarray(forced, dtype=np.int64).reshape(-1).astype(np.int32))
+    S = int(steps)
+    order = np.empty(max(S, 0), dtype=np.int32)
+    path = np.empty((max(S, 0), 3))
+    coef = np.empty((max(S, 0), K))
+    rc = lib.fsnap_omp_gram(K, _ptr(Q), _ptr(q), float(y2), _ptr(ref), omp_criterion(criterion),
+                            _ptr(forced) if forced.size else None, forced.size, S, _ptr(order), _ptr(path), _ptr(coef))
+    raise_status(rc, "" if rc != E_ARG else f"fsnap_omp_gram: bad argument (K = {K}, steps = {S}, forced = {forced.tolist()})")
+    return order, path, coef
 
 
 def rowspace_chain(factors, z, rcond, active=None):
@@ -1178,6 +1218,25 @@ class HipContext:
         self._check(self._lib.fsnap_lasso_path(self._h, K, F, int(nsub), c_void_p(d_stats_ptr), _ptr(alphas) if Q else None, Q,
                                                int(max_iter), float(tol), _ptr(coef), _ptr(info), _ptr(held)))
         return coef, info, held
+
+    def omp_path(self, d_stats_ptr: int, K: int, F: int, nsub: int, criterion, forced, steps: int, levels):
+        """Grouped K-fold greedy forward-selection path on per-fold statistics in device memory (``fsnap_omp_path``, K <= 144,
+        steps <= min(K, 128)): ``d_stats_ptr`` as for ``lasso_path``; ``criterion`` "omp" / "ols"; ``forced``: columns taken
+        first, in order; ``levels``: the ascending step counts at which coefficients are returned.  Returns (order ((F + 1) x
+        steps, int32; index F: no fold left out; -1 once a path has ended), path ((F + 1) x steps x 3: e_s, score, pivot),
+        heldout (F x steps x 3: n_f, weighted squared error of fold f under its own refit after s steps, bb_f), coef ((F + 1)
+        x Q x K at the levels))."""
+        forced = np.ascontiguousarray(np.asarray(forced, dtype=np.int64).reshape(-1).astype(np.int32))
+        levels = np.ascontiguousarray(np.asarray(levels, dtype=np.int64).reshape(-1).astype(np.int32))
+        K, F, S, Q = int(K), int(F), int(steps), levels.size
+        order = np.empty((max(F, 0) + 1, max(S, 0)), dtype=np.int32)
+        path = np.empty((max(F, 0) + 1, max(S, 0), 3))
+        held = np.empty((max(F, 0), max(S, 0), 3))
+        coef = np.empty((max(F, 0) + 1, Q, max(K, 0)))
+        self._check(self._lib.fsnap_omp_path(self._h, K, F, int(nsub), c_void_p(d_stats_ptr), omp_criterion(criterion),
+                                             _ptr(forced) if forced.size else None, forced.size, S, _ptr(levels) if Q else None, Q,
+                                             _ptr(order), _ptr(path), _ptr(held), _ptr(coef)))
+        return order, path, held, coef
 
     def ard_path(self, d_stats_ptr: int, K: int, F: int, nsub: int, hyper, max_iter: int, tol: float):
         """Grouped K-fold ARD threshold path on per-fold statistics in device memory (``fsnap_ard_path``, K <= 144):

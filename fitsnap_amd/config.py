@@ -15,6 +15,8 @@ defaulted here, with the reference's defaults:
   [LASSO]  alpha=1.0E-8, max_iter=2000                      (solver_sections/lasso.py:13-14)
   [ROBUST] loss=huber, tune (per loss), alpha=1.0E-8, scale_by=row_type, scale_iters=0, max_iter=50, tol=1.0E-8
                                                             (solvers/robust.py; no counterpart in the reference)
+  [OMP]    terms, criterion=ols, forced= (comma-separated column indices)
+                                                            (solvers/omp.py; no counterpart in the reference)
   [EXTRAS] apply_transpose, multinode_testing, only_test, dump_*   (extras.py:19-45)
   [CALCULATOR] calculator, energy, force, stress, per_atom_energy, linear
                                                             (calculator_sections/calculator.py:17-32)
@@ -209,6 +211,25 @@ class Config:
                 not_used("LASSO")
             self.sections["LASSO"] = SimpleNamespace(name="LASSO", alpha=_get(ld, "alpha", "1.0E-8", "float"),
                                                      max_iter=_get(ld, "max_iter", "2000", "int"))
+
+        if "OMP" in raw or solver.upper() == "OMP":
+            od = raw.get("OMP", {})
+            _check_keys("OMP", od, ["terms", "criterion", "forced"])
+            if solver.upper() != "OMP":
+                not_used("OMP")
+            forced = od.get("forced", next((v for k, v in od.items() if k.lower() == "forced"), ""))
+            if isinstance(forced, str):
+                forced = [x for x in forced.replace(",", " ").split()]
+            forced = [int(x) for x in forced]
+            if len(set(forced)) != len(forced) or any(j < 0 for j in forced):
+                raise RuntimeError(f">>> [OMP] forced = {forced}: column indices must be >= 0 and distinct")
+            criterion = _get(od, "criterion", "ols", "str").strip().lower()
+            if criterion not in ("omp", "ols"):
+                raise RuntimeError(f">>> [OMP] criterion = {criterion}: one of omp, ols")
+            terms = _get(od, "terms", "0", "int")           # 0: every column (the fit ends where the candidates do)
+            if terms < 0:
+                raise RuntimeError(f">>> [OMP] terms = {terms}: at least 1 (or 0 for every column)")
+            self.sections["OMP"] = SimpleNamespace(name="OMP", terms=terms, criterion=criterion, forced=tuple(forced))
 
         if "ROBUST" in raw or solver.upper() == "ROBUST":
             rb = raw.get("ROBUST", {})

@@ -3199,6 +3199,66 @@ int fsnap_ard_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const dou
     return FSNAP_OK;                                        // a failed problem is its own status 1, not the call's
 }
 
+// ---- grouped K-fold greedy forward-selection paths on the per-fold statistics (kernel S1 of fsnap_lasso.hip, O1 of fsnap_omp.hip)
+
+int fsnap_omp_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const double* d_stats, int criterion,
+                   const int32_t* forced, int64_t nforced, int64_t S, const int32_t* levels, int64_t Q, int32_t* order_out,
+                   double* path_out, double* heldout_out, double* coef_out) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_omp_path";
+    if (!d_stats || !levels || !order_out || !path_out || !heldout_out || !coef_out || (nforced > 0 && !forced))
+        return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
+    if (K < 1 || K > fsnap::OMP_MAX_K) return ctx->fail(FSNAP_E_ARG, "%s: K = %lld (1 ... %d)", who, (long long)K, fsnap::OMP_MAX_K);
+    if (S < 1 || S > K || S > fsnap::OMP_MAX_S)
+        return ctx->fail(FSNAP_E_ARG, "%s: S = %lld (1 ... min(K, %d))", who, (long long)S, fsnap::OMP_MAX_S);
+    if (F < 1 || nsub < 1 || F > 0x3FFFFFF || nsub > 0x3FFFFFFF)
+        return ctx->fail(FSNAP_E_ARG, "%s: F = %lld, nsub = %lld", who, (long long)F, (long long)nsub);
+    if (Q < 1 || Q > 0xFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: Q = %lld", who, (long long)Q);
+    if (criterion != FSNAP_OMP_OMP && criterion != FSNAP_OMP_OLS) return ctx->fail(FSNAP_E_ARG, "%s: criterion = %d", who, criterion);
+    for (int64_t i = 0; i < Q; ++i)
+        if (levels[i] < 1 || levels[i] > S || (i > 0 && levels[i] < levels[i - 1]))
+            return ctx->fail(FSNAP_E_ARG, "%s: levels[%lld] = %d (ascending, 1 ... %lld)", who, (long long)i, (int)levels[i], (long long)S);
+    if (nforced < 0 || nforced > K) return ctx->fail(FSNAP_E_ARG, "%s: nforced = %lld", who, (long long)nforced);
+    for (int64_t i = 0; i < nforced; ++i) {
+        bool bad = forced[i] < 0 || forced[i] >= K;
+        for (int64_t k = 0; k < i && !bad; ++k) bad = forced[k] == forced[i];
+        if (bad) return ctx->fail(FSNAP_E_ARG, "%s: forced[%lld] = %d is out of range or repeated", who, (long long)i, (int)forced[i]);
+    }
+    if (!cand_fits(F * nsub, K))
+        return ctx->fail(FSNAP_E_ARG, "%s: %lld blocks x %lld doubles exceed FSNAP_CAT_STATS_MAX_BYTES", who, (long long)(F * nsub),
+                         (long long)FSNAP_PACKED_LEN(K));
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    const int64_t T = FSNAP_PACKED_LEN(K), nprob = F + 1;
+    const int64_t nfold = nsub > 1 ? F : 0;                 // nsub = 1: the caller's blocks are the folds
+    if (!ctx->lasso_sys.ensure((size_t)(nfold + 1) * T * 8) || !ctx->omp_in.ensure((size_t)(nforced + Q) * 4) ||
+        !ctx->omp_order.ensure((size_t)nprob * S * 4) || !ctx->omp_path.ensure((size_t)nprob * S * 3 * 8) ||
+        !ctx->omp_held.ensure((size_t)F * S * 3 * 8) || !ctx->omp_coef.ensure((size_t)nprob * Q * K * 8))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(omp path) failed");
+    double* dfolds = nfold ? (double*)ctx->lasso_sys.p : nullptr;
+    double* dtotal = (double*)ctx->lasso_sys.p + nfold * T;
+    int* dforced = nforced ? (int*)ctx->omp_in.p : nullptr;
+    int* dlevels = (int*)ctx->omp_in.p + nforced;
+    if (nforced)
+        FSNAP_HIP(hipMemcpyAsync(dforced, forced, (size_t)nforced * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(forced)");
+    FSNAP_HIP(hipMemcpyAsync(dlevels, levels, (size_t)Q * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(levels)");
+    FSNAP_HIP(fsnap::launch_lasso_folds(d_stats, (int)F, (int)nsub, (int)K, dfolds, dtotal, ctx->stream),
+              "launch fsnap_lasso_folds_k");
+    const int nblocks = (int)std::min<int64_t>(nprob, (int64_t)fsnap::omp_blocks_per_cu((int)K, (int)S) * std::max(1, ctx->num_cu));
+    FSNAP_HIP(fsnap::launch_omp_path(nblocks, dfolds ? dfolds : d_stats, dtotal, (int)K, (int)F, criterion, dforced, (int)nforced,
+                                     (int)S, dlevels, (int)Q, (int*)ctx->omp_order.p, (double*)ctx->omp_path.p,
+                                     (double*)ctx->omp_held.p, (double*)ctx->omp_coef.p, ctx->stream),
+              "launch fsnap_omp_path_k");
+    FSNAP_HIP(hipMemcpyAsync(order_out, ctx->omp_order.p, (size_t)nprob * S * 4, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(order)");
+    FSNAP_HIP(hipMemcpyAsync(path_out, ctx->omp_path.p, (size_t)nprob * S * 3 * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(path)");
+    FSNAP_HIP(hipMemcpyAsync(heldout_out, ctx->omp_held.p, (size_t)F * S * 3 * 8, hipMemcpyDeviceToHost, ctx->stream),
+              "hipMemcpy(heldout)");
+    FSNAP_HIP(hipMemcpyAsync(coef_out, ctx->omp_coef.p, (size_t)nprob * Q * K * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(coef)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    for (int64_t i = 0; i < nprob * Q * K; ++i)
+        if (!std::isfinite(coef_out[i])) return FSNAP_NUM_NONFINITE;
+    return FSNAP_OK;
+}
+
 // ---- grouped K-fold cross-validation of weight candidates (kernels V0, V1, V2 of fsnap_cv.hip) -----------------------------
 
 int fsnap_cv_candidates(fsnap_ctx* ctx, int64_t layout, double alpha, const double* S, int P, int F, int C, int64_t K,

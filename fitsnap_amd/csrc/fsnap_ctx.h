@@ -155,6 +155,9 @@ struct fsnap_ctx {
     // fsnap_ard_path: hyper-parameters, coefficients, lambdas, info, held-out sums (the fold sums live in lasso_sys); kept
     // between calls
     DevBuf ard_hyper, ard_coef, ard_lambda, ard_info, ard_held;
+    // fsnap_omp_path: [forced | levels], orders, path rows, held-out sums, coefficients (the fold sums live in lasso_sys); kept
+    // between calls
+    DevBuf omp_in, omp_order, omp_path, omp_held, omp_coef;
     // fsnap_cv_candidates / fsnap_cv_candidate_rows: per-category totals followed by the F C blocks total - fold, scales, coefficients, info, the per-fold coefficient
     // tables of a launch (the chunk partials and sums share cand_rpart / cand_res); kept between calls
     DevBuf cv_total, cv_S, cv_coef, cv_info, cv_betaT;

@@ -311,6 +311,20 @@ int ard_blocks_per_cu(int K);
 hipError_t launch_ard_path(int nblocks, const double* folds, const double* total, const double* hyper, int K, int F, int Q,
                            int max_iter, double tol, double* coef, double* lambda, double* info, double* heldout, hipStream_t st);
 
+// Grouped K-fold greedy forward-selection paths (fsnap_omp.hip; K <= OMP_MAX_K, S <= OMP_MAX_S) on the folds and the total of
+// kernel S1.  Kernel O1: problem f (f = F: no fold left out) is fsnap_omp_gram on (total - folds[f]) with diag_ref = the
+// total's diagonal, statement for statement: order[f][S], path[f][S][3] = (e_s, score, pivot), coef[f][Q][K] at the steps
+// levels[Q] (ascending, 1 ... S), heldout[f][S][3] (f < F) = (n_f, bb_f - 2 beta . c_f + beta^T G_f beta, bb_f) after every
+// step.  forced[nforced] (may be nullptr with nforced = 0) and levels: device.  One wave per workgroup, nblocks workgroups
+// stride over the problems; LDS holds W (S rows of an odd stride >= K), z, beta and one dense coefficient row.
+constexpr int OMP_MAX_K = 144;
+constexpr int OMP_MAX_S = 128;
+size_t omp_lds_bytes(int K, int S);
+int omp_blocks_per_cu(int K, int S);
+hipError_t launch_omp_path(int nblocks, const double* folds, const double* total, int K, int F, int criterion, const int* forced,
+                           int nforced, int S, const int* levels, int Q, int* order, double* path, double* heldout, double* coef,
+                           hipStream_t st);
+
 // Grouped K-fold cross-validation of weight candidates (fsnap_cv.hip; V1: K <= CV_MAX_K) on the F * C packed blocks of
 // fsnap_cat_normal_eq with composite category f * C + c.  Kernel V0: total[c] = sum_f stats[f * C + c], folds in index order,
 // and rest[f * C + c] = total[c] - stats[f * C + c] (F C blocks).

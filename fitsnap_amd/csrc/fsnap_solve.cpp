@@ -1448,3 +1448,115 @@ extern "C" int fsnap_lasso_gram(int64_t K64, const double* Q, const double* q, d
     if (gap_out) *gap_out = gap;
     return all_finite(w, n) ? FSNAP_OK : FSNAP_NUM_NONFINITE;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Greedy forward selection on the statistics: orthogonal matching pursuit (score r_j^2 / Q_jj) and its orthogonal-least-squares
+// form (score r_j^2 / t_j, forward stepwise regression).  No counterpart in the reference.  The recurrence is a left-looking
+// Cholesky factorisation of Q whose pivot is chosen by the score, with q carried along: row s of W is the pivot row of the
+// factor over ALL columns, so t_k = Q_kk - sum_u W_uk^2 is what column k has left outside the span of the support and
+// r_k = q_k - sum_u W_uk z_u its correlation with the residual.  The coefficients of every step come from the triangle
+// L[v][u] = W[u][j_v] by back substitution.  Kernel O1 (fsnap_omp.hip) runs these statements one for one -- every multiply-add
+// an explicit fma, every sum with u ascending -- so order, path and coef agree with it to the bit.
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" int fsnap_omp_gram(int64_t K64, const double* Q, const double* q, double y2, const double* diag_ref, int criterion,
+                              const int32_t* forced, int64_t nforced, int64_t S64, int32_t* order, double* path, double* coef) {
+    if (!Q || !q || !order || !path || !coef || K64 < 1 || K64 > (1 << 20) || S64 < 1 || S64 > K64) return FSNAP_E_ARG;
+    if (criterion != FSNAP_OMP_OMP && criterion != FSNAP_OMP_OLS) return FSNAP_E_ARG;
+    if (nforced < 0 || nforced > K64 || (nforced > 0 && !forced)) return FSNAP_E_ARG;
+    const int n = (int)K64, S = (int)S64;
+    std::vector<unsigned char> seen((size_t)n, 0);
+    for (int64_t i = 0; i < nforced; ++i) {
+        if (forced[i] < 0 || forced[i] >= n || seen[forced[i]]) return FSNAP_E_ARG;
+        seen[forced[i]] = 1;
+    }
+    if (!all_finite(Q, (size_t)n * n) || !all_finite(q, n) || !std::isfinite(y2)) return FSNAP_NUM_NONFINITE;
+    if (diag_ref && !all_finite(diag_ref, n)) return FSNAP_NUM_NONFINITE;
+    const double tol = 1e-10;                               // fsnap::LOCO_PIVOT_TOL
+    const bool ols = criterion == FSNAP_OMP_OLS;
+    vec W((size_t)S * n), r((size_t)n), t((size_t)n), qd((size_t)n), z((size_t)S), x((size_t)S), acc((size_t)n);
+    std::vector<unsigned char> alive((size_t)n), cand((size_t)n);
+    for (int j = 0; j < n; ++j) {
+        const double qjj = Q[(size_t)j * n + j], ref = diag_ref ? diag_ref[j] : qjj;
+        alive[j] = !(ref == 0.0 || qjj <= tol * ref);
+        cand[j] = alive[j];
+        qd[j] = alive[j] ? qjj : 0.0;
+        t[j] = qd[j];
+        r[j] = alive[j] ? q[j] : 0.0;
+    }
+    double e_cur = y2;
+    int64_t fpos = 0;
+    int ns = 0;
+    bool ended = false;
+    for (int s = 0; s < S; ++s) {
+        int js = -1;
+        double sc_out = 0.0, pv_out = 0.0;
+        if (!ended) {
+            for (int j = 0; j < n; ++j)
+                if (cand[j] && t[j] <= tol * qd[j]) cand[j] = 0;
+            while (fpos < nforced && js < 0) {
+                const int j = forced[fpos++];
+                if (cand[j]) js = j;
+            }
+            if (js < 0) {
+                double bs = -1.0;
+                for (int j = 0; j < n; ++j)
+                    if (cand[j]) {
+                        const double sc = r[j] * r[j] / (ols ? t[j] : qd[j]);
+                        if (sc > bs) {
+                            bs = sc;
+                            js = j;
+                        }
+                    }
+            }
+            if (js < 0) ended = true;
+        }
+        double* cs = coef + (size_t)s * n;
+        if (js >= 0) {
+            const double tj = t[js], rj = r[js];
+            const double l = std::sqrt(tj);
+            const double zs = rj / l;
+            sc_out = rj * rj / (ols ? tj : qd[js]);
+            pv_out = tj;
+            const double* Qj = Q + (size_t)js * n;
+            for (int k = 0; k < n; ++k) acc[k] = alive[k] ? Qj[k] : 0.0;
+            for (int u = 0; u < ns; ++u) {
+                const double* __restrict__ wu = W.data() + (size_t)u * n;
+                const double a = wu[js];
+                double* __restrict__ ac = acc.data();
+                for (int k = 0; k < n; ++k) ac[k] = std::fma(-a, wu[k], ac[k]);
+            }
+            double* wn = W.data() + (size_t)ns * n;
+            for (int k = 0; k < n; ++k) {
+                const double w = alive[k] ? acc[k] / l : 0.0;
+                wn[k] = w;
+                r[k] = std::fma(-w, zs, r[k]);
+                t[k] = std::fma(-w, w, t[k]);
+            }
+            cand[js] = 0;
+            e_cur = std::fma(-zs, zs, e_cur);
+            z[ns] = zs;
+            order[s] = js;
+            ++ns;
+            // L^T beta = z, L[v][u] = W[u][j_v]: column-oriented back substitution from the last row up
+            for (int p = 0; p < ns; ++p) x[p] = z[p];
+            for (int v = ns - 1; v >= 0; --v) {
+                const int jv = order[v];
+                const double bv = x[v] / W[(size_t)v * n + jv];
+                x[v] = bv;
+                for (int p = 0; p < v; ++p) x[p] = std::fma(-W[(size_t)p * n + jv], bv, x[p]);
+            }
+            for (int k = 0; k < n; ++k) cs[k] = 0.0;
+            for (int p = 0; p < ns; ++p) cs[order[p]] = x[p];
+        } else {
+            order[s] = -1;
+            if (s > 0)
+                std::memcpy(cs, cs - n, (size_t)n * sizeof(double));
+            else
+                for (int k = 0; k < n; ++k) cs[k] = 0.0;
+        }
+        path[(size_t)s * 3 + 0] = e_cur;
+        path[(size_t)s * 3 + 1] = sc_out;
+        path[(size_t)s * 3 + 2] = pv_out;
+    }
+    return all_finite(coef, (size_t)S * n) ? FSNAP_OK : FSNAP_NUM_NONFINITE;
+}

@@ -25,7 +25,7 @@ import numpy as np
 
 from .. import _capi
 from .._hostblas import blas_threads
-from . import ard_path, influence, lasso_path, loco, loco_uq, ridge_path, select, select_joint, uq
+from . import ard_path, influence, lasso_path, loco, loco_uq, omp_path, ridge_path, select, select_joint, uq
 
 
 class _TrainWeights:
@@ -1275,6 +1275,35 @@ class Solver:
         ``cv_se`` of it.  Neither the fit nor the config is changed.  Raises ValueError for other solvers, for
         ``apply_transpose``, for an empty grid and for unknown grid keys."""
         return ard_path.ard_path(self, grid, folds, by, fs_dict, b, w, tol, max_iter, method, table, seed)
+
+    # ------------------------------------------------------------------------------
+    # grouped K-fold greedy sparse-selection paths (solvers/omp_path.py, csrc/fsnap_omp.hip)
+    # ------------------------------------------------------------------------------
+    def omp_path(self, max_terms, levels=None, criterion="ols", forced=(), folds=5, by="Configs", fs_dict=None, b=None, w=None,
+                 method="auto", table="auto", seed=0):
+        """Grouped K-fold cross-validation of greedy forward selection -- "the best s of the K columns, and which s" --
+        after ``perform_fit`` of an OMP solver, from ONE pass over the resident training rows: the units (``fs_dict[by]``,
+        as in ``loco_errors``) are dealt into folds as in ``lasso_path``, the statistics of every fold are formed on the GPU
+        and every fold-left-out refit plus the fit on all rows runs ``max_terms`` steps of the selection on "total minus
+        fold": a Cholesky factorisation whose pivot is chosen by ``criterion`` -- "omp" (orthogonal matching pursuit:
+        the column most correlated with the residual, scikit-learn's ``orthogonal_mp_gram`` on normalised columns) or "ols"
+        (orthogonal least squares, forward stepwise: the column that lowers the residual most) -- after the ``forced``
+        columns, which are taken first and in order.  Every size carries the unshrunk least-squares fit on its support.
+        ``levels``: the sizes at which coefficients are kept and tabled (None: a short geometric ladder 1, 2, 3, 4, 6, 8,
+        ... up to ``max_terms``).  ``method``: "device" (the kernel, K <= 144 and ``max_terms`` <= 128), "host"
+        (``fsnap_omp_gram`` over the downloaded fold statistics, any K) or "auto" (the kernel where it exists; both routes give
+        the same bits in orders, fits and training errors).  ``folds``, ``table``, labels, truths and weights as in ``lasso_path``; the table is keyed
+        (terms, Row_Type) at the levels.  Collective on several ranks; a unit may span ranks.
+        Returns ``OmpPath(terms, order, fold_orders, levels, fits, train_sse, table, fold_of_unit, cv_error, cv_se, best,
+        best_terms, sparsest, sparsest_terms, frequency)``: ``terms`` 1 ... max_terms; ``order`` the columns in the order
+        the fit on all rows chose them (-1 once no candidate was left) and ``fold_orders`` (F x max_terms) those of the
+        refits; ``fits`` (Q x K) the coefficients on all rows at the levels and ``train_sse`` their weighted squared
+        training error after every step; ``cv_error`` the pooled weighted held-out mean squared error after every step and
+        ``cv_se`` its standard error over the folds; ``best`` the index of the minimum (ties to fewer terms),
+        ``best_terms`` its size, ``sparsest`` / ``sparsest_terms`` the fewest terms within one ``cv_se`` of it;
+        ``frequency`` per column the share of the refits that chose it within ``best_terms`` steps.  Neither the fit nor
+        the config is changed.  Raises ValueError for other solvers and for ``apply_transpose``."""
+        return omp_path.omp_path(self, max_terms, levels, criterion, forced, folds, by, fs_dict, b, w, method, table, seed)
 
     # ------------------------------------------------------------------------------
     # robust M-estimator fits by IRLS (solvers/robust.py, csrc/fsnap_robust.hip)

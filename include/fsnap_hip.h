@@ -475,6 +475,31 @@ int fsnap_lasso_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const d
 int fsnap_ard_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const double* d_stats, const double* hyper, int64_t Q,
                    int64_t max_iter, double tol, double* coef_out, double* lambda_out, double* info_out, double* heldout_out);
 
+/* Grouped K-fold greedy forward-selection paths on per-fold statistics (kernel S1 of csrc/fsnap_lasso.hip, O1 of
+ * csrc/fsnap_omp.hip; the folds, the host route, the picks and the tables are solvers/omp_path.py).  d_stats (DEVICE), the folds
+ * and the total T as for fsnap_lasso_path.  Problem f < F: the refit without fold f; f = F: the fit on all training rows:
+ *     Qm = T.G - G_f,  qv = T.c - c_f,  y2 = T.bb - bb_f                                                 (f = F: T alone)
+ * run through fsnap_omp_gram's recurrence (below) with diag_ref = T.G_jj for S steps: a Cholesky factorisation of Qm whose pivot
+ * is chosen by `criterion` (FSNAP_OMP_OMP / FSNAP_OMP_OLS) after the `forced` columns (host, nforced >= 0 indices in order;
+ * may be NULL when nforced = 0), with the right-hand side carried along.  levels (host): Q sparsity levels in ascending order,
+ * each in 1 ... S; the coefficients are returned at those only.  Outputs (host): order_out[(F + 1)][S] = the column chosen at
+ * step s (-1 once the path has ended); path_out[(F + 1)][S][3] = e_s, the score and the pivot t_j* of the chosen column (the
+ * last e_s, 0, 0 once the path has ended); heldout_out[F][S][3] = n_f, h_{f,s} = bb_f - 2 beta . c_f + beta^T G_f beta (the
+ * weighted squared error of fold f under its own refit after s steps; the last one once the path has ended, bb_f when it took
+ * no step), bb_f; coef_out[(F + 1)][Q][K] = the unshrunk least-squares coefficients on the support after levels[q] steps (the
+ * last support's once the path has ended), zero elsewhere.  FSNAP_E_ARG for K outside 1 ... 144, S < 1, S > min(K, 128), F < 1,
+ * nsub < 1, Q < 1, levels that decrease or leave 1 ... S, a forced index out of range or repeated, nforced < 0, an unknown
+ * criterion, a NULL pointer, or F * nsub blocks past FSNAP_CAT_STATS_MAX_BYTES.  fp64, one wave per problem, no atomics; every
+ * sum runs in an order that depends on the problem alone and the argmax compares the fp64 scores exactly (lowest index on
+ * equality): bit-identical run to run and under any permutation or subset of the folds; order_out, path_out and coef_out carry
+ * the bits of fsnap_omp_gram on the same system.  The resident rows, weights, mask and category layout are not touched.
+ * Synchronous. */
+#define FSNAP_OMP_OMP 0   /* score_j = r_j^2 / Qm_jj: orthogonal matching pursuit on the column-normalised system */
+#define FSNAP_OMP_OLS 1   /* score_j = r_j^2 / t_j:   orthogonal least squares (forward stepwise regression)       */
+int fsnap_omp_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const double* d_stats, int criterion,
+                   const int32_t* forced, int64_t nforced, int64_t S, const int32_t* levels, int64_t Q, int32_t* order_out,
+                   double* path_out, double* heldout_out, double* coef_out);
+
 /* Joint scores of units (normally configurations) of the resident rows for active learning (kernels J1, J2 of
  * csrc/fsnap_joint.hip, fp64 MFMA; the host algebra is solvers/select_joint.py).  With the posterior C = M M^T (M: K x J),
  * the noise variance tau of a unit-weight row, the weighted rows X_u = diag(omega) A_u (n_u x K) of unit u, Z = X_u M and a
@@ -579,6 +604,26 @@ int fsnap_cond_info(double info[4]);
  * *n_iter / *gap (may be NULL): sweeps run and the last duality gap.  Host side, no context needed. */
 int fsnap_lasso_gram(int64_t K, const double* Q, const double* q, double y_norm2, double l1_reg, int64_t max_iter, double tol,
                      double* w, int64_t* n_iter, double* gap);
+
+/* Greedy forward selection on the statistics (orthogonal matching pursuit and its orthogonal-least-squares form): the
+ * unshrunk least-squares fit on a nested, ordered list of columns, one column more per step.  Q (K x K, row-major, symmetric),
+ * q and y2 = |y|^2 are X^T X, X^T y and y^T y of the rows.  Column j is dead -- never chosen, coefficient 0 -- when
+ * diag_ref[j] == 0 or Q_jj <= 1e-10 diag_ref[j] (diag_ref = NULL: Q's own diagonal, so only a column with Q_jj <= 0 is).
+ * State: t_j = Q_jj, r_j = q_j, e_0 = y2.  Step s = 1 ... S: the candidates are the live columns neither chosen nor struck; a
+ * candidate with t_j <= 1e-10 Q_jj is struck for good (it lies in the span of the support).  While `forced` (nforced indices
+ * in order; may be NULL when nforced = 0) is not exhausted its next entry is taken if it is a candidate and skipped without a
+ * step if not; otherwise j* = argmax score_j, score_j = r_j^2 / Q_jj (FSNAP_OMP_OMP) or r_j^2 / t_j (FSNAP_OMP_OLS), an exact
+ * tie going to the lowest index.  Then, for every live column k (dead: w_k = 0),
+ *     l = sqrt(t_j*),  w_k = (Q_{j*,k} - sum_{u<s} W_{u,j*} W_{u,k}) / l,  z_s = r_j* / l,
+ *     r_k -= w_k z_s,  t_k -= w_k^2,  e_s = e_{s-1} - z_s^2,  row s of W = w
+ * (sums with u ascending, one fma per term).  The coefficients after s steps solve L^T beta_S = z_{1..s}, L[v][u] = W_{u,j_v},
+ * by column-oriented back substitution from the last row up.  Without a candidate the path ends: later order entries are -1,
+ * later path rows (the last e_s, 0, 0) and later coefficient rows repeat the last step's (zeros when no step was taken).
+ * Outputs: order[S]; path[S][3] = e_s, the score and the pivot t_j* of the chosen column; coef[S][K].  FSNAP_E_ARG for K < 1,
+ * S outside 1 ... K, an unknown criterion, nforced < 0, a forced index out of range or repeated, a NULL pointer;
+ * FSNAP_NUM_NONFINITE for a NaN/Inf in the statistics.  Host side, no context needed. */
+int fsnap_omp_gram(int64_t K, const double* Q, const double* q, double y2, const double* diag_ref, int criterion,
+                   const int32_t* forced, int64_t nforced, int64_t S, int32_t* order, double* path, double* coef);
 
 /* Same solve, taking the packed statistics [G | c | ...] from DEVICE memory (the buffer
  * fsnap_normal_eq_async / the all-reduce left in HBM).  Small systems are copied to the host
