@@ -129,6 +129,10 @@ SIGNATURES = {
     "fsnap_candidate_rows": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p]),
     "fsnap_cv_candidates": (c_int, [c_void_p, c_int64, c_double, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p]),
     "fsnap_cv_candidate_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int64, c_void_p]),
+    "fsnap_cv_candidates_grad": (c_int, [c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64,
+                                         c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fsnap_cv_candidates_grad_rhs": (c_int, [c_void_p, c_int64, c_void_p]),
+    "fsnap_cv_candidates_grad_times": (c_int, [c_void_p, c_void_p]),
     "fsnap_row_variance": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "fsnap_row_variance_device": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
@@ -873,6 +877,42 @@ class HipContext:
         self._check(self._lib.fsnap_cv_candidate_rows(self._h, int(layout), _ptr(coef) if coef.size else None, int(P), int(F),
                                                       int(C), self.K, _ptr(out) if out.size else None))
         return out
+
+    def cv_candidates_grad(self, layout: int, alpha: float, S, omega, coef, want_lambda=False):
+        """The adjoint gradient of a cross-validated cost over the scales (``fsnap_cv_candidates_grad``, K <= 144): S and
+        omega (P, C), coef (P, F, K) the refits of ``cv_candidates`` for the same layout, alpha and S.  Returns (grad_S (P, C) =
+        dJ/dS, grad_log_alpha (P,), lambda (P, F, K) or None, info (P, F, 2): status, smallest scaled pivot).  A candidate
+        with a status-1 problem has a NaN row."""
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        omega = np.ascontiguousarray(omega, dtype=np.float64)
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        if S.ndim != 2 or omega.shape != S.shape:
+            raise ValueError("S and omega must both be (P, C)")
+        P, C = S.shape
+        if coef.ndim != 3 or coef.shape[0] != P:
+            raise ValueError("coef must be (P, F, K)")
+        F, K = coef.shape[1], coef.shape[2]
+        grad = np.empty((P, C))
+        gla = np.empty(P)
+        lam = np.empty((P, F, K)) if want_lambda else None
+        info = np.empty((P, F, 2))
+        self._check(self._lib.fsnap_cv_candidates_grad(
+            self._h, int(layout), float(alpha), _ptr(S) if S.size else None, _ptr(omega) if omega.size else None,
+            _ptr(coef) if coef.size else None, int(P), int(F), int(C), int(K), _ptr(grad) if grad.size else None,
+            _ptr(gla) if gla.size else None, _ptr(lam) if lam is not None and lam.size else None, _ptr(info) if info.size else None))
+        return grad, gla, lam, info
+
+    def cv_candidates_grad_times(self):
+        """(V0 + G1 RHS, G2, G1 bilinear) device milliseconds of the last ``cv_candidates_grad`` call."""
+        ms = np.empty(3)
+        self._check(self._lib.fsnap_cv_candidates_grad_times(self._h, _ptr(ms)))
+        return ms
+
+    def cv_candidates_grad_rhs(self, P: int, F: int, K: int):
+        """g (P, F, K), the adjoint right-hand sides of the last ``cv_candidates_grad`` call (tests and diagnostics)."""
+        g = np.empty((int(P), int(F), int(K)))
+        self._check(self._lib.fsnap_cv_candidates_grad_rhs(self._h, g.size, _ptr(g)))
+        return g
 
     # -- row-space least squares --------------------------------------------------------
     def row_variance(self, M, mode=UQ_QUAD, beta=None, scale=None, cat=None, ncat=0, want_var=True, want_preds=False):

@@ -852,6 +852,8 @@ int fsnap_ctx_destroy(fsnap_ctx* ctx) {
     if (ctx->h2d_ev) (void)hipEventDestroy(ctx->h2d_ev);
     if (ctx->chol_host) (void)hipHostFree(ctx->chol_host);
     if (ctx->chol_ev) (void)hipEventDestroy(ctx->chol_ev);
+    for (auto& ev : ctx->cvg_ev)
+        if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : ctx->ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto& sl : ctx->ring)
@@ -3344,6 +3346,132 @@ int fsnap_cv_candidate_rows(fsnap_ctx* ctx, int64_t layout, const double* coef, 
         FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");   // bt is rewritten for the next group
     }
     FSNAP_HIP(hipMemcpyAsync(out, ctx->cand_res.p, (size_t)P * nout * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(out)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    return FSNAP_OK;
+}
+
+// ---- gradient of the cross-validated cost over the candidates' scales (kernels G1, G2 of fsnap_cvgrad.hip) -------------------
+
+int fsnap_cv_candidates_grad(fsnap_ctx* ctx, int64_t layout, double alpha, const double* S, const double* omega, const double* coef,
+                             int P, int F, int C, int64_t K, double* grad_S_out, double* grad_log_alpha_out, double* lambda_out,
+                             double* info_out) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_cv_candidates_grad";
+    if (!S || !omega || !coef || !grad_S_out || !grad_log_alpha_out || !info_out) return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
+    if (K < 1 || K > fsnap::CV_MAX_K) return ctx->fail(FSNAP_E_ARG, "%s: K = %lld (1 ... %d)", who, (long long)K, fsnap::CV_MAX_K);
+    if (F < 2 || C < 1 || P < 1) return ctx->fail(FSNAP_E_ARG, "%s: P = %d, F = %d, C = %d", who, P, F, C);
+    if (!std::isfinite(alpha) || alpha < 0.0) return ctx->fail(FSNAP_E_ARG, "%s: alpha = %g is negative or not finite", who, alpha);
+    if (layout <= 0 || layout != ctx->cand_layout || ctx->cand_stats_K <= 0 || !ctx->cand_stats.p)
+        return ctx->fail(FSNAP_E_STATE, "%s: no per-category statistics of layout %lld on the context (fsnap_cat_prepare + "
+                                        "fsnap_cat_normal_eq first)", who, (long long)layout);
+    if ((int64_t)F * C != ctx->cand_ncat || K != ctx->cand_stats_K)
+        return ctx->fail(FSNAP_E_ARG, "%s: F * C = %lld, K = %lld but the statistics have %d categories of order %lld", who,
+                         (long long)F * C, (long long)K, ctx->cand_ncat, (long long)ctx->cand_stats_K);
+    const int64_t nprob = (int64_t)P * F, K8 = (K + 7) / 8 * 8, tiles = ((int64_t)P + 15) / 16;
+    const int64_t ntab = tiles * F * K8 * 16, nD = tiles * F * C * 16;
+    if (nprob > FSNAP_CV_MAX_PROBLEMS || (double)ntab * 8.0 > (double)FSNAP_CAT_STATS_MAX_BYTES ||
+        (double)nD * 8.0 > (double)FSNAP_CAT_STATS_MAX_BYTES || F > 65535 || tiles * F * C >= ((int64_t)1 << 24))
+        return ctx->fail(FSNAP_E_ARG, "%s: P * F = %lld problems of %lld coefficients and %d categories (at most %d problems, "
+                                      "FSNAP_CAT_STATS_MAX_BYTES of coefficient tables and of per-category terms)", who,
+                         (long long)nprob, (long long)K, C, FSNAP_CV_MAX_PROBLEMS);
+    for (int64_t i = 0; i < (int64_t)P * C; ++i)
+        if (!std::isfinite(S[i]) || !std::isfinite(omega[i]))
+            return ctx->fail(FSNAP_E_ARG, "%s: S or omega [%lld][%lld] is not finite", who, (long long)(i / C), (long long)(i % C));
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    const int64_t T = FSNAP_PACKED_LEN(K);
+    ctx->cvg_g_len = 0;
+    if (!ctx->cv_total.ensure((size_t)(C + (int64_t)F * C) * T * 8) || !ctx->cv_S.ensure((size_t)P * C * 8) ||
+        !ctx->cvg_betaT.ensure((size_t)ntab * 8) || !ctx->cvg_lamT.ensure((size_t)ntab * 8) ||
+        !ctx->cvg_omegaT.ensure((size_t)tiles * C * 16 * 8) || !ctx->cvg_g.ensure((size_t)nprob * K * 8) ||
+        !ctx->cvg_lam.ensure((size_t)nprob * K * 8) || !ctx->cvg_D.ensure((size_t)nD * 8) || !ctx->cvg_info.ensure((size_t)nprob * 2 * 8))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(candidate cross-validation gradient) failed");
+    // the zero-padded tables of every 16-candidate tile: candidate 16 tile + e in slot e
+    std::vector<double> bt((size_t)ntab, 0.0), ot((size_t)tiles * C * 16, 0.0);
+    for (int p = 0; p < P; ++p) {
+        const int64_t tile = p >> 4, e = p & 15;
+        for (int f = 0; f < F; ++f)
+            for (int64_t k = 0; k < K; ++k) bt[(size_t)(((tile * F + f) * K8 + k) * 16 + e)] = coef[((int64_t)p * F + f) * K + k];
+        for (int c = 0; c < C; ++c) ot[(size_t)((tile * C + c) * 16 + e)] = omega[(int64_t)p * C + c];
+    }
+    FSNAP_HIP(hipMemcpyAsync(ctx->cv_S.p, S, (size_t)P * C * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(S)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->cvg_betaT.p, bt.data(), bt.size() * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(coef)");
+    FSNAP_HIP(hipMemcpyAsync(ctx->cvg_omegaT.p, ot.data(), ot.size() * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(omega)");
+    FSNAP_HIP(hipMemsetAsync(ctx->cvg_lamT.p, 0, (size_t)ntab * 8, ctx->stream), "hipMemsetAsync");
+    const double* stats = (const double*)ctx->cand_stats.p;
+    double* total = (double*)ctx->cv_total.p;
+    double* rest = total + (int64_t)C * T;
+    for (auto& ev : ctx->cvg_ev)
+        if (!ev) FSNAP_HIP(hipEventCreate(&ev), "hipEventCreate");
+    FSNAP_HIP(hipEventRecord(ctx->cvg_ev[0], ctx->stream), "hipEventRecord");
+    // kernel V0 again: the blocks of a tag may have been formed anew since the last fsnap_cv_candidates, and one elementwise
+    // pass is small next to the two sweeps below
+    FSNAP_HIP(fsnap::launch_cv_total(stats, F, C, (int)K, total, rest, ctx->stream), "launch fsnap_cv_total_k");
+    FSNAP_HIP(fsnap::launch_cvgrad_rhs(stats, (const double*)ctx->cvg_betaT.p, (const double*)ctx->cvg_omegaT.p, P, F, C, (int)K,
+                                       (double*)ctx->cvg_g.p, ctx->stream),
+              "launch fsnap_cvgrad_rhs_k");
+    FSNAP_HIP(hipEventRecord(ctx->cvg_ev[1], ctx->stream), "hipEventRecord");
+    const int nblocks = (int)std::min<int64_t>(nprob, (int64_t)fsnap::cv_blocks_per_cu((int)K) * std::max(1, ctx->num_cu));
+    FSNAP_HIP(fsnap::launch_cvgrad_solve(nblocks, rest, total, (const double*)ctx->cv_S.p, (const double*)ctx->cvg_g.p, P, F, C, (int)K,
+                                         alpha, (double*)ctx->cvg_lam.p, (double*)ctx->cvg_lamT.p, (double*)ctx->cvg_info.p,
+                                         ctx->stream),
+              "launch fsnap_cvgrad_solve_k");
+    FSNAP_HIP(hipEventRecord(ctx->cvg_ev[2], ctx->stream), "hipEventRecord");
+    FSNAP_HIP(fsnap::launch_cvgrad_bilinear(rest, (const double*)ctx->cvg_betaT.p, (const double*)ctx->cvg_lamT.p, P, F, C, (int)K,
+                                            (double*)ctx->cvg_D.p, ctx->stream),
+              "launch fsnap_cvgrad_bilinear_k");
+    FSNAP_HIP(hipEventRecord(ctx->cvg_ev[3], ctx->stream), "hipEventRecord");
+    std::vector<double> lam((size_t)nprob * K), D((size_t)nD);
+    FSNAP_HIP(hipMemcpyAsync(lam.data(), ctx->cvg_lam.p, lam.size() * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(lambda)");
+    FSNAP_HIP(hipMemcpyAsync(D.data(), ctx->cvg_D.p, D.size() * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(D)");
+    FSNAP_HIP(hipMemcpyAsync(info_out, ctx->cvg_info.p, (size_t)nprob * 2 * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(info)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    for (int i = 0; i < 3; ++i) {
+        float ms = 0.0f;
+        FSNAP_HIP(hipEventElapsedTime(&ms, ctx->cvg_ev[i], ctx->cvg_ev[i + 1]), "hipEventElapsedTime");
+        ctx->cvg_ms[i] = ms;
+    }
+    // the sums over the folds, f in index order; lambda . beta with k ascending, one fma per term
+    for (int p = 0; p < P; ++p) {
+        const int64_t tile = p >> 4, e = p & 15;
+        for (int c = 0; c < C; ++c) {
+            double s = 0.0;
+            for (int f = 0; f < F; ++f) s += D[(size_t)(((tile * F + f) * C + c) * 16 + e)];
+            grad_S_out[(int64_t)p * C + c] = 2.0 * S[(int64_t)p * C + c] * s;
+        }
+        double la = 0.0;
+        for (int f = 0; f < F; ++f) {
+            const double* l = lam.data() + ((int64_t)p * F + f) * K;
+            const double* b = coef + ((int64_t)p * F + f) * K;
+            double d = 0.0;
+            for (int64_t k = 0; k < K; ++k) d = std::fma(l[k], b[k], d);
+            la += d;
+        }
+        grad_log_alpha_out[p] = -alpha * la;
+    }
+    if (lambda_out) std::copy(lam.begin(), lam.end(), lambda_out);
+    ctx->cvg_g_len = nprob * K;
+    return FSNAP_OK;                                        // a failed problem is its own status 1 and a NaN gradient row
+}
+
+int fsnap_cv_candidates_grad_times(fsnap_ctx* ctx, double* ms_out) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_cv_candidates_grad_times";
+    if (!ms_out) return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
+    if (ctx->cvg_g_len <= 0) return ctx->fail(FSNAP_E_STATE, "%s: no fsnap_cv_candidates_grad call to read from", who);
+    for (int i = 0; i < 3; ++i) ms_out[i] = ctx->cvg_ms[i];
+    return FSNAP_OK;
+}
+
+int fsnap_cv_candidates_grad_rhs(fsnap_ctx* ctx, int64_t n, double* g_out) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_cv_candidates_grad_rhs";
+    if (!g_out) return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
+    if (ctx->cvg_g_len <= 0 || !ctx->cvg_g.p) return ctx->fail(FSNAP_E_STATE, "%s: no fsnap_cv_candidates_grad call to read from", who);
+    if (n != ctx->cvg_g_len)
+        return ctx->fail(FSNAP_E_ARG, "%s: n = %lld but the last call left P * F * K = %lld doubles", who, (long long)n,
+                         (long long)ctx->cvg_g_len);
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    FSNAP_HIP(hipMemcpyAsync(g_out, ctx->cvg_g.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(g)");
     FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
     return FSNAP_OK;
 }

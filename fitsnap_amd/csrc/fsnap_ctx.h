@@ -161,6 +161,12 @@ struct fsnap_ctx {
     // fsnap_cv_candidates / fsnap_cv_candidate_rows: per-category totals followed by the F C blocks total - fold, scales, coefficients, info, the per-fold coefficient
     // tables of a launch (the chunk partials and sums share cand_rpart / cand_res); kept between calls
     DevBuf cv_total, cv_S, cv_coef, cv_info, cv_betaT;
+    // fsnap_cv_candidates_grad: coefficient tables [tile][f][K8][16], omega tables [tile][C][16], g[P F][K], lambda[P F][K],
+    // lambda tables [tile][f][K8][16], D[tile][f][c][16], info[P F][2] (totals and scales share cv_total / cv_S); kept between calls
+    DevBuf cvg_betaT, cvg_omegaT, cvg_g, cvg_lam, cvg_lamT, cvg_D, cvg_info;
+    hipEvent_t cvg_ev[4] = {};   // around kernels V0 + G1 (RHS), G2 and G1 (bilinear) of the last call
+    double cvg_ms[3] = {};       // their times in ms (fsnap_cv_candidates_grad_times)
+    int64_t cvg_g_len = 0;       // doubles of g the last fsnap_cv_candidates_grad left (0: none), for fsnap_cv_candidates_grad_rhs
     // fsnap_joint_*: the session's unit-sorted row index, unit offsets and per-position weights (uploaded once by begin), the
     // padded factor [M | M B] and B, Z / Pi per position (npos x Wp), the bucketed list of live units, per-unit (gain, reduction)
     // and info, per-workgroup scratch (S and the right-hand-side fragments of units too large for LDS); the host keeps the

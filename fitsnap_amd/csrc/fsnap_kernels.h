@@ -344,6 +344,22 @@ hipError_t launch_cv_solve(int nblocks, const double* rest, const double* total,
 hipError_t launch_cv_rows(const double* A, int64_t lda, const double* b, const double* w0, const int* idx, const CatChunk* chunks,
                           int64_t nchunks, int K, int C, const double* betaT, double* partial, hipStream_t st);
 
+// Gradient of the cross-validated cost over the candidates' scales (fsnap_cvgrad.hip, K <= CV_MAX_K), on the blocks stats[f * C + c]
+// and rest[f * C + c] above.  Candidates come in tiles of 16: betaT / lamT[tile][f][K8][16] (K8 = K rounded up to 8) and
+// omegaT[tile][C][16] are zero-padded tables, candidate 16 tile + e in slot e.
+// Kernel G1 (RHS epilogue):      g[(16 tile + e) F + f][K] = 2 sum_c omega[c][e] (stats[f C + c].G beta[f][.][e] - stats[f C + c].r)
+//                                (the categories in four contiguous quarters of ceil(C / 4), each c ascending, added in index order)
+// Kernel G2: problem p F + f is kernel V1's system with g as the right-hand side: lam[P F][K] (0 on dead columns, NaN with status
+//            1), the same value into lamT, info[P F][2] = (status, smallest scaled pivot)
+// Kernel G1 (bilinear epilogue): D[((tile F + f) C + c) 16 + e] = lam[f][.][e] . (rest[f C + c].r - rest[f C + c].G beta[f][.][e])
+// All pointers: device.
+hipError_t launch_cvgrad_rhs(const double* stats, const double* betaT, const double* omegaT, int P, int F, int C, int K, double* g,
+                             hipStream_t st);
+hipError_t launch_cvgrad_solve(int nblocks, const double* rest, const double* total, const double* S, const double* g, int P, int F,
+                               int C, int K, double alpha, double* lam, double* lamT, double* info, hipStream_t st);
+hipError_t launch_cvgrad_bilinear(const double* rest, const double* betaT, const double* lamT, int P, int F, int C, int K, double* D,
+                                  hipStream_t st);
+
 // Joint unit scores (fsnap_joint.hip).  Kernel J1: for the npos positions of the unit-sorted row index idx,
 // ZP[p] = om[p] a_idx[p] [M | M B] (Wp doubles per position; Fp: device, Kp x Wp row-major, zero-padded: columns [0, Jp) the
 // factor M, columns [Jp, Wp) the target block M B; Wp = Jp without a target; om: the weight of every position).

@@ -134,7 +134,7 @@ class CandidateFits:
         self.info = []
         self._layout = None          # tag of this object's category layout on the context (fsnap_cat_prepare)
         self._packed = None          # (context, device address, K, P) of the last fit's packed candidate statistics
-        self._cv = None              # (tag, composite categories, F) of cross_validate's fold x category layout
+        self._cv = None              # (tag, composite categories, F, device address of the blocks) of cross_validate's layout
         self._cv_folds = None        # (key, composite categories, fold_of_unit, F, rows per composite category) of its last folds
 
     @staticmethod
@@ -224,10 +224,10 @@ class CandidateFits:
                 ctx = self._push_base()
                 tag = ctx.cat_prepare(ccat, F * self.ncat)
             if self.pt.multi:
-                tag, _ = ctx.cat_normal_eq_dist(tag, self.K, F * self.ncat)
+                tag, ptr = ctx.cat_normal_eq_dist(tag, self.K, F * self.ncat)
             else:
-                ctx.cat_normal_eq(tag)
-            self._cv = (tag, ccat, F)
+                ptr = ctx.cat_normal_eq(tag)
+            self._cv = (tag, ccat, F, ptr)
         return ctx
 
     def cross_validate(self, S, folds=5, by="Configs", seed=0, method="auto"):
@@ -252,6 +252,40 @@ class CandidateFits:
         from . import candidates_cv
 
         return candidates_cv.cross_validate(self, S, folds, by, seed, method)
+
+    def cross_validate_gradient(self, S, weights, metric="rmse", folds=5, by="Configs", seed=0, method="auto"):
+        """The cross-validated cost of the candidates S (P x ncat) and its exact gradient over S (solvers/candidates_cv_grad.py).
+        The cost is J[p] = sum_t weights[t] phi(E[p, t] / n_t) over the row types, E the BASE-weighted held-out sum (w0 r)^2 of
+        the training rows of type t (no scaling by S), phi = sqrt for ``metric="rmse"``, the identity for ``"mse"``; with
+        w0 = 1 it is ``cross_validate(S).cost(weights, "rmse")`` exactly.  The S-scaled sums are not used: they go to 0 with S.
+        ``weights``, ``folds``, ``by``, ``seed`` as in ``cross_validate`` / ``CandidateCV.cost``.
+
+        Returns a ``CandidateCVGradient``: ``cv`` (the ``CandidateCV`` of the same call, device route up to 144 columns),
+        ``cost`` (P,), ``grad_S`` = dJ/dS and ``grad_log`` = dJ/dlog|S| (P, ncat), ``grad_log_alpha`` (P,) = dJ/dlog alpha
+        ([RIDGE] alpha; 0 for SVD), ``omega``, ``status`` (P, F).  The gradient is the adjoint of the K x K Cholesky solve of
+        every refit on its live columns, the live set treated as fixed: one more solve per fold and two sweeps over the
+        per-(fold, category) blocks for all ncat derivatives.  ``method="device"``: ``fsnap_cv_candidates_grad`` (kernels G1, G2
+        of csrc/fsnap_cvgrad.hip, K <= 144); ``"host"``: the numpy restatement from the downloaded blocks; ``"auto"``: the
+        device up to 144 columns, the host beyond.  A candidate with any status-1 fold has NaN cost and a NaN gradient row
+        under every method: the adjoint of the truncating composed solve that ``cross_validate(method="auto")`` falls back to
+        is not defined here.  Collective in a multi-rank job; every rank returns the same bits.  Like ``cross_validate`` the
+        call leaves the composite layout on the context."""
+        from . import candidates_cv_grad
+
+        return candidates_cv_grad.cross_validate_gradient(self, S, weights, metric, folds, by, seed, method)
+
+    def descend_weights(self, S0, weights, metric="rmse", steps=20, folds=5, by="Configs", seed=0, eta0=0.5, c1=1e-4,
+                        max_halvings=8):
+        """Batched steepest descent of the cross-validated cost on theta = log|S| from the P starts S0 (P x ncat) at once: per
+        iteration one ``cross_validate_gradient`` call, then line-search rounds of one ``cross_validate`` call over the P trial
+        points S exp(-eta grad_log).  Candidate p accepts a trial when its cost is <= cost_p - c1 eta_p |grad_log_p|^2 (Armijo);
+        otherwise eta_p is halved, at most ``max_halvings`` times per iteration; eta_p doubles after an accepted step.
+        Categories with S = 0 stay 0 (their log-gradient is 0), signs are kept, a candidate with a NaN cost stays where it is.
+        Returns (S (P, ncat), cost history (steps + 1, P), accepted step sizes (steps, P), 0 where no step was taken).
+        Deterministic and collective.  Deliberately plain: no L-BFGS, no bounds, no step over alpha."""
+        from . import candidates_cv_grad
+
+        return candidates_cv_grad.descend_weights(self, S0, weights, metric, steps, folds, by, seed, eta0, c1, max_halvings)
 
     # ------------------------------------------------------------------------------
     def fit(self, S):

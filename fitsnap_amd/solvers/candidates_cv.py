@@ -93,9 +93,10 @@ class CandidateCV:
     coefficients); ``min_pivot`` (P, F): smallest pivot of the Jacobi-scaled matrix (NaN where the composed route solved);
     ``route`` (P, F) of "device" / "composed"; ``fold_of_unit``: {unit: fold}; ``sums`` (P, C, 5): per candidate and category
     of ``keys`` the pooled n, sum|r|, sum r^2, sum|w r|, sum (w r)^2 of the held-out rows, w = w0 S[p, c] (testing categories
-    hold no row); ``row_types``: the row types in sorted order."""
+    hold no row); ``row_types``: the row types in sorted order; ``base_sums`` (P, C, 5): the same sums with the base weights
+    w0 alone (no scaling by S), the sums the objective of ``cross_validate_gradient`` is taken on (None when not given)."""
 
-    def __init__(self, coef, status, min_pivot, route, fold_of_unit, sums, keys, S):
+    def __init__(self, coef, status, min_pivot, route, fold_of_unit, sums, keys, S, base_sums=None):
         self.coef = coef
         self.status = status
         self.min_pivot = min_pivot
@@ -104,6 +105,7 @@ class CandidateCV:
         self.sums = sums
         self.keys = list(keys)
         self.S = S
+        self.base_sums = base_sums
         self.row_types = sorted({k[2] for k in self.keys})
 
     def _groups(self):
@@ -239,12 +241,15 @@ def cross_validate(cf, S, folds=5, by="Configs", seed=0, method="auto"):
         else:
             sums4 = ctx.cv_candidate_rows(tag, coef, C)
         pooled = pool_heldout(sums4, counts, S, F)
+        base = pool_heldout(sums4, counts, np.ones_like(S), F)
     else:
         pooled = np.zeros((P, C, 5))
+        base = np.zeros((P, C, 5))
     if cf.pt.multi:
-        pooled = np.ascontiguousarray(pooled)
-        cf.pt.allreduce_host(pooled.reshape(-1))
-    return CandidateCV(coef, status, min_pivot, route, dict(fold_of_unit), pooled, cf.keys, S)
+        both = np.ascontiguousarray(np.stack([pooled, base]))        # one elementwise all-reduce for the two
+        cf.pt.allreduce_host(both.reshape(-1))
+        pooled, base = both[0], both[1]
+    return CandidateCV(coef, status, min_pivot, route, dict(fold_of_unit), pooled, cf.keys, S, base)
 
 
 def composed_fits(cf, ctx, tag, kind, param, Sc):

@@ -826,6 +826,42 @@ int fsnap_cv_candidates(fsnap_ctx* ctx, int64_t layout, double alpha, const doub
  * Synchronous. */
 int fsnap_cv_candidate_rows(fsnap_ctx* ctx, int64_t layout, const double* coef, int P, int F, int C, int64_t K, double* out);
 
+/* Gradient of a cross-validated cost over the scales S (kernels G1, G2 of csrc/fsnap_cvgrad.hip; the objective and omega are
+ * solvers/candidates_cv_grad.py).  For a cost J[p] = sum_t wt[t] phi(E[p][t] / n_t) of the base-weighted held-out sums
+ * E[p][t] = sum (w0 r)^2 over the training categories of row type t, the caller passes omega[p][c] = dJ/dE of the type of
+ * category c (host, P x C, finite; 0 for categories that take no part) and coef[p][f][K] = the refits of fsnap_cv_candidates for the
+ * same layout, alpha and S (host; NaN where a refit failed).  With B[f][c] the blocks, R[f][c] = T[c] - B[f][c] and
+ * H = sum_c S[p][c]^2 R[f][c].G + alpha I on the live columns of problem (p, f) (the live rule above; the live set is treated as
+ * fixed, dead columns have beta_j = lambda_j = 0):
+ *     g[p][f]      = 2 sum_c omega[p][c] (B[f][c].G beta[p][f] - B[f][c].r)       (four quarters of ceil(C / 4) categories, c ascending
+ *                                                                                  in each, added in index order; per c, k in steps of 8)
+ *     lambda[p][f] = H^-1 g[p][f]                          (kernel V1's Jacobi-scaled Cholesky, live rule and pivot rule)
+ *     D[p][f][c]   = lambda[p][f] . (R[f][c].r - R[f][c].G beta[p][f])            (rows ascending per wave, waves in index order)
+ *     grad_S_out[p][c]      = 2 S[p][c] sum_f D[p][f][c]                          (f in index order, on the host)
+ *     grad_log_alpha_out[p] = -alpha sum_f lambda[p][f] . beta[p][f]              (k ascending, then f in index order, on the host)
+ * grad_S_out is dJ/dS[p][c] (defined at S = 0 and for negative S; dJ/dlog|S| = S dJ/dS), grad_log_alpha_out dJ/dlog alpha.
+ * Scaling every S[p][.]^2 and alpha by one factor changes no beta, so sum_c S dJ/dS = -2 dJ/dlog alpha.  Both sweeps over the
+ * blocks run on v_mfma_f64_16x16x4_f64 for 16 candidates at a time: a block is read once per 16 candidates.  lambda_out (host,
+ * P x F x K, may be NULL) receives lambda; info_out[P][F][2] = status (0 / 1) and the smallest scaled pivot of the adjoint solve,
+ * those of the refit.  A problem of status 1 has NaN lambda: the gradient row and grad_log_alpha of ITS candidate are NaN, no
+ * other candidate changes; the call still returns FSNAP_OK.  T[c] and R[f][c] are formed again from the blocks the context holds
+ * (kernel V0).  Arguments, state and limits as fsnap_cv_candidates (K <= 144; also the coefficient tables, 16 ceil(P / 16) F K
+ * doubles, and 16 ceil(P / 16) F C doubles of D within FSNAP_CAT_STATS_MAX_BYTES); a non-finite omega is FSNAP_E_ARG.  fp64, no
+ * atomics; every sum runs in an order fixed by the problem alone: a candidate's bits do not depend on the batch, the grid or the
+ * run.  Nothing resident is touched.  Synchronous. */
+int fsnap_cv_candidates_grad(fsnap_ctx* ctx, int64_t layout, double alpha, const double* S, const double* omega, const double* coef,
+                             int P, int F, int C, int64_t K, double* grad_S_out, double* grad_log_alpha_out, double* lambda_out,
+                             double* info_out);
+
+/* The adjoint right-hand sides g[P][F][K] (above) of the last successful fsnap_cv_candidates_grad call on this context, for tests
+ * and diagnostics: g_out (host) receives n = P * F * K doubles.  FSNAP_E_STATE without such a call, FSNAP_E_ARG when n is not
+ * its P * F * K.  Synchronous. */
+int fsnap_cv_candidates_grad_rhs(fsnap_ctx* ctx, int64_t n, double* g_out);
+
+/* Device times of the last successful fsnap_cv_candidates_grad call on this context, from events on its stream: ms_out[3] =
+ * kernels V0 + G1 (RHS epilogue), kernel G2, kernel G1 (bilinear epilogue), in milliseconds.  FSNAP_E_STATE without such a call. */
+int fsnap_cv_candidates_grad_times(fsnap_ctx* ctx, double* ms_out);
+
 /* ---- multi-GPU: one process per GPU; RCCL or one-shot peer-to-peer over xGMI -------- */
 
 /* The reference's data-parallel form of this path (examples/library/transpose_trick/example.py:230-254): every MPI
