@@ -22,6 +22,7 @@
 
 #include <cmath>
 
+#include "fsnap_fold_body.h"
 #include "fsnap_kernels.h"
 #include "fsnap_wave_sum.h"
 
@@ -157,7 +158,6 @@ __global__ __launch_bounds__(ARD_THREADS) void fsnap_ard_path_k(const double* __
                                                                 double* __restrict__ info_out, double* __restrict__ heldout) {
     extern __shared__ __attribute__((aligned(16))) double ard_lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t T = (int64_t)K * K + K + 3;
     const int KK = K * K;
     ArdLds s;
     s.tri = ard_lds;
@@ -194,19 +194,17 @@ __global__ __launch_bounds__(ARD_THREADS) void fsnap_ard_path_k(const double* __
 
     for (int p = blockIdx.x; p < nprob; p += gridDim.x) {
         const int f = p / Q;
-        const double* Gf = f < F ? folds + (int64_t)f * T : nullptr;
-        const double bb_f = Gf ? Gf[KK + K] : 0.0, n_f = Gf ? Gf[KK + K + 2] : 0.0;
-        const double y2 = Gf ? total[KK + K] - bb_f : total[KK + K];
-        const double n = Gf ? total[KK + K + 2] - n_f : total[KK + K + 2];
+        const FoldView fv = fold_view(folds, total, f, F, K);
+        const double* Gf = fv.Gf;
+        const double y2 = fv.y2, n = fv.n;
         const double* hy = hyper + (int64_t)p * 6;
         const double alpha_1 = hy[0], alpha_2 = hy[1], lambda_1 = hy[2], lambda_2 = hy[3], thr = hy[4];
         double alpha = hy[5];
-        // dead columns: the total never touched the column, or the subtraction left noise
         if (tid < K) {
             const int64_t at = (int64_t)tid * K + tid;
             const double tjj = total[at];
             const double qjj = Gf ? tjj - Gf[at] : tjj;
-            const bool dead = tjj == 0.0 || qjj <= pivot_tol * tjj;
+            const bool dead = fold_dead(tjj, qjj, pivot_tol);
             s.dsc[tid] = dead ? 1.0 : sqrt(qjj);
             s.lam[tid] = 1.0;
             s.coef[tid] = 0.0;
@@ -326,12 +324,8 @@ __global__ __launch_bounds__(ARD_THREADS) void fsnap_ard_path_k(const double* __
             if (wave == 0) {
                 const double s1 = sum_by_wave(K, lane, [&](int e) { return s.coef[e] * Gf[KK + e]; });
                 const double s2 = sum_by_wave(K, lane, [&](int e) { return s.coef[e] * s.rv[e]; });
-                if (lane == 0) {
-                    double* ho = heldout + (int64_t)p * 3;            // p = f Q + q for f < F
-                    ho[0] = n_f;
-                    ho[1] = bb_f - 2.0 * s1 + s2;
-                    ho[2] = bb_f;
-                }
+                // p = f Q + q for f < F
+                if (lane == 0) fold_heldout_store(heldout + (int64_t)p * 3, fv.n_f, fv.bb_f - 2.0 * s1 + s2, fv.bb_f);
             }
         }
         __syncthreads();                                              // the next problem refills the vectors

@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <limits>
 #include <new>
 #include <queue>
@@ -2086,6 +2087,55 @@ bool cand_fits(int64_t n, int64_t K) {
     return n > 0 && K > 0 && (double)n * (double)FSNAP_PACKED_LEN(K) * 8.0 <= (double)FSNAP_CAT_STATS_MAX_BYTES;
 }
 
+// The front that fsnap_lasso_path, fsnap_ard_path and fsnap_omp_path share ("The fold frame").  fold_check: the
+// arguments they have in common, ahead of the entry point's own -- the statistics, K against the kernel's limit, F folds of
+// nsub blocks, Q, and (F + 1) per_fold problems (per_fold: Q, or 1 where a problem walks all Q levels).  fold_stage: the size
+// cap, the device, ctx->fold_sys and kernel S1; *folds are the F fold blocks (d_stats itself with nsub = 1, where the caller's
+// blocks are the folds) and *total their sum.  fold_grid: the workgroups of a grid-stride launch over nprob problems.
+// fold_finish: the copies back, the wait, and the scan of one output (nscan doubles; none: nullptr) for non-finite values.
+int fold_check(fsnap_ctx* ctx, const char* who, int64_t K, int max_K, int64_t F, int64_t nsub, int64_t Q, int64_t per_fold,
+               const double* d_stats) {
+    if (!d_stats) return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
+    if (K < 1 || K > max_K) return ctx->fail(FSNAP_E_ARG, "%s: K = %lld (1 ... %d)", who, (long long)K, max_K);
+    if (F < 1 || nsub < 1 || F > 0x3FFFFFFF || nsub > 0x3FFFFFFF)
+        return ctx->fail(FSNAP_E_ARG, "%s: F = %lld, nsub = %lld", who, (long long)F, (long long)nsub);
+    if (Q < 1 || Q > 0xFFFFF || (F + 1) * per_fold > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: Q = %lld", who, (long long)Q);
+    return FSNAP_OK;
+}
+
+int fold_stage(fsnap_ctx* ctx, const char* who, int64_t K, int64_t F, int64_t nsub, const double* d_stats, const double** folds,
+               const double** total) {
+    if (!cand_fits(F * nsub, K))
+        return ctx->fail(FSNAP_E_ARG, "%s: %lld blocks x %lld doubles exceed FSNAP_CAT_STATS_MAX_BYTES", who, (long long)(F * nsub),
+                         (long long)FSNAP_PACKED_LEN(K));
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    const int64_t T = FSNAP_PACKED_LEN(K);
+    const int64_t nfold = nsub > 1 ? F : 0;                 // nsub = 1: the caller's blocks are the folds
+    if (!ctx->fold_sys.ensure((size_t)(nfold + 1) * T * 8)) return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(fold sums) failed");
+    double* dfolds = nfold ? (double*)ctx->fold_sys.p : nullptr;
+    double* dtotal = (double*)ctx->fold_sys.p + nfold * T;
+    FSNAP_HIP(fsnap::launch_fold_sums(d_stats, (int)F, (int)nsub, (int)K, dfolds, dtotal, ctx->stream),
+              "launch fsnap_fold_sums_k");
+    *folds = dfolds ? dfolds : d_stats;
+    *total = dtotal;
+    return FSNAP_OK;
+}
+
+int fold_grid(const fsnap_ctx* ctx, int64_t nprob, int per_cu) {
+    return (int)std::min<int64_t>(nprob, (int64_t)per_cu * std::max(1, ctx->num_cu));
+}
+
+struct FoldCopy { void* host; const void* dev; size_t bytes; };
+
+int fold_finish(fsnap_ctx* ctx, std::initializer_list<FoldCopy> copies, const double* scan, int64_t nscan) {
+    for (const FoldCopy& c : copies)
+        FSNAP_HIP(hipMemcpyAsync(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(fold path results)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    for (int64_t i = 0; i < nscan; ++i)
+        if (!std::isfinite(scan[i])) return FSNAP_NUM_NONFINITE;
+    return FSNAP_OK;
+}
+
 // kernels C1 + C1R into ctx->cand_stats (the rows must be prepared)
 int cand_stats_launch(fsnap_ctx* ctx) {
     const int K = (int)ctx->K, ncat = ctx->cand_ncat;
@@ -3109,45 +3159,31 @@ int fsnap_lasso_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const d
                      int64_t max_iter, double tol, double* coef_out, double* info_out, double* heldout_out) {
     if (!ctx) return FSNAP_E_ARG;
     const char* who = "fsnap_lasso_path";
-    if (!d_stats || !alphas || !coef_out || !info_out || !heldout_out) return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
-    if (K < 1 || K > fsnap::LASSO_MAX_K)
-        return ctx->fail(FSNAP_E_ARG, "%s: K = %lld (1 ... %d)", who, (long long)K, fsnap::LASSO_MAX_K);
-    if (F < 1 || nsub < 1 || F > 0x3FFFFFFF || nsub > 0x3FFFFFFF)
-        return ctx->fail(FSNAP_E_ARG, "%s: F = %lld, nsub = %lld", who, (long long)F, (long long)nsub);
-    if (Q < 1 || Q > 0xFFFFF || (F + 1) * Q > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: Q = %lld", who, (long long)Q);
+    if (!alphas || !coef_out || !info_out || !heldout_out) return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
+    int rc = fold_check(ctx, who, K, fsnap::LASSO_MAX_K, F, nsub, Q, Q, d_stats);
+    if (rc) return rc;
     if (max_iter < 1 || max_iter > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: max_iter = %lld", who, (long long)max_iter);
     if (!std::isfinite(tol) || tol < 0.0) return ctx->fail(FSNAP_E_ARG, "%s: tol = %g is negative or not finite", who, tol);
     for (int64_t q = 0; q < Q; ++q)
         if (!std::isfinite(alphas[q]) || alphas[q] < 0.0)
             return ctx->fail(FSNAP_E_ARG, "%s: alphas[%lld] = %g is negative or not finite", who, (long long)q, alphas[q]);
-    if (!cand_fits(F * nsub, K))
-        return ctx->fail(FSNAP_E_ARG, "%s: %lld blocks x %lld doubles exceed FSNAP_CAT_STATS_MAX_BYTES", who, (long long)(F * nsub),
-                         (long long)FSNAP_PACKED_LEN(K));
-    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-    const int64_t T = FSNAP_PACKED_LEN(K), nprob = (F + 1) * Q;
-    const int64_t nfold = nsub > 1 ? F : 0;                 // nsub = 1: the caller's blocks are the folds
-    if (!ctx->lasso_sys.ensure((size_t)(nfold + 1) * T * 8) || !ctx->lasso_alphas.ensure((size_t)Q * 8) ||
-        !ctx->lasso_coef.ensure((size_t)nprob * K * 8) || !ctx->lasso_info.ensure((size_t)nprob * 4 * 8) ||
-        !ctx->lasso_held.ensure((size_t)F * Q * 3 * 8))
+    const double *dfolds, *dtotal;
+    if ((rc = fold_stage(ctx, who, K, F, nsub, d_stats, &dfolds, &dtotal))) return rc;
+    const int64_t nprob = (F + 1) * Q;
+    if (!ctx->lasso_alphas.ensure((size_t)Q * 8) || !ctx->lasso_coef.ensure((size_t)nprob * K * 8) ||
+        !ctx->lasso_info.ensure((size_t)nprob * 4 * 8) || !ctx->lasso_held.ensure((size_t)F * Q * 3 * 8))
         return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(lasso path) failed");
-    double* dfolds = nfold ? (double*)ctx->lasso_sys.p : nullptr;
-    double* dtotal = (double*)ctx->lasso_sys.p + nfold * T;
     FSNAP_HIP(hipMemcpyAsync(ctx->lasso_alphas.p, alphas, (size_t)Q * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(alphas)");
-    FSNAP_HIP(fsnap::launch_lasso_folds(d_stats, (int)F, (int)nsub, (int)K, dfolds, dtotal, ctx->stream),
-              "launch fsnap_lasso_folds_k");
-    const int nblocks = (int)std::min<int64_t>(nprob, (int64_t)fsnap::lasso_blocks_per_cu((int)K) * std::max(1, ctx->num_cu));
-    FSNAP_HIP(fsnap::launch_lasso_cd(nblocks, dfolds ? dfolds : d_stats, dtotal, (const double*)ctx->lasso_alphas.p, (int)K, (int)F,
-                                     (int)Q, (int)max_iter, tol, (double*)ctx->lasso_coef.p, (double*)ctx->lasso_info.p,
-                                     (double*)ctx->lasso_held.p, ctx->stream),
+    FSNAP_HIP(fsnap::launch_lasso_cd(fold_grid(ctx, nprob, fsnap::lasso_blocks_per_cu((int)K)), dfolds, dtotal,
+                                     (const double*)ctx->lasso_alphas.p, (int)K, (int)F, (int)Q, (int)max_iter, tol,
+                                     (double*)ctx->lasso_coef.p, (double*)ctx->lasso_info.p, (double*)ctx->lasso_held.p,
+                                     ctx->stream),
               "launch fsnap_lasso_cd_k");
-    FSNAP_HIP(hipMemcpyAsync(coef_out, ctx->lasso_coef.p, (size_t)nprob * K * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(coef)");
-    FSNAP_HIP(hipMemcpyAsync(info_out, ctx->lasso_info.p, (size_t)nprob * 4 * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(info)");
-    FSNAP_HIP(hipMemcpyAsync(heldout_out, ctx->lasso_held.p, (size_t)F * Q * 3 * 8, hipMemcpyDeviceToHost, ctx->stream),
-              "hipMemcpy(heldout)");
-    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    for (int64_t i = 0; i < nprob * K; ++i)
-        if (!std::isfinite(coef_out[i])) return FSNAP_NUM_NONFINITE;
-    return FSNAP_OK;
+    return fold_finish(ctx,
+                       {{coef_out, ctx->lasso_coef.p, (size_t)nprob * K * 8},
+                        {info_out, ctx->lasso_info.p, (size_t)nprob * 4 * 8},
+                        {heldout_out, ctx->lasso_held.p, (size_t)F * Q * 3 * 8}},
+                       coef_out, nprob * K);
 }
 
 // ---- grouped K-fold ARD threshold paths on the per-fold statistics (kernel S1 of fsnap_lasso.hip, A1 of fsnap_ard.hip) ----
@@ -3156,12 +3192,9 @@ int fsnap_ard_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const dou
                    int64_t max_iter, double tol, double* coef_out, double* lambda_out, double* info_out, double* heldout_out) {
     if (!ctx) return FSNAP_E_ARG;
     const char* who = "fsnap_ard_path";
-    if (!d_stats || !hyper || !coef_out || !lambda_out || !info_out || !heldout_out)
-        return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
-    if (K < 1 || K > fsnap::ARD_MAX_K) return ctx->fail(FSNAP_E_ARG, "%s: K = %lld (1 ... %d)", who, (long long)K, fsnap::ARD_MAX_K);
-    if (F < 1 || nsub < 1 || F > 0x3FFFFFFF || nsub > 0x3FFFFFFF)
-        return ctx->fail(FSNAP_E_ARG, "%s: F = %lld, nsub = %lld", who, (long long)F, (long long)nsub);
-    if (Q < 1 || Q > 0xFFFFF || (F + 1) * Q > 0x3FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: Q = %lld", who, (long long)Q);
+    if (!hyper || !coef_out || !lambda_out || !info_out || !heldout_out) return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
+    int rc = fold_check(ctx, who, K, fsnap::ARD_MAX_K, F, nsub, Q, Q, d_stats);
+    if (rc) return rc;
     if (max_iter < 1 || max_iter > 0x7FFFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: max_iter = %lld", who, (long long)max_iter);
     if (!std::isfinite(tol) || tol < 0.0) return ctx->fail(FSNAP_E_ARG, "%s: tol = %g is negative or not finite", who, tol);
     const int64_t nprob = (F + 1) * Q;
@@ -3171,34 +3204,25 @@ int fsnap_ard_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const dou
         if (!std::isfinite(h) || h < 0.0 || (i % 6 >= 4 && h <= 0.0))
             return ctx->fail(FSNAP_E_ARG, "%s: hyper[%lld][%lld] = %g", who, (long long)(i / 6), (long long)(i % 6), h);
     }
-    if (!cand_fits(F * nsub, K))
-        return ctx->fail(FSNAP_E_ARG, "%s: %lld blocks x %lld doubles exceed FSNAP_CAT_STATS_MAX_BYTES", who, (long long)(F * nsub),
-                         (long long)FSNAP_PACKED_LEN(K));
-    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-    const int64_t T = FSNAP_PACKED_LEN(K);
-    const int64_t nfold = nsub > 1 ? F : 0;                 // nsub = 1: the caller's blocks are the folds
-    if (!ctx->lasso_sys.ensure((size_t)(nfold + 1) * T * 8) || !ctx->ard_hyper.ensure((size_t)nprob * 6 * 8) ||
-        !ctx->ard_coef.ensure((size_t)nprob * K * 8) || !ctx->ard_lambda.ensure((size_t)nprob * K * 8) ||
-        !ctx->ard_info.ensure((size_t)nprob * 6 * 8) || !ctx->ard_held.ensure((size_t)F * Q * 3 * 8))
+    const double *dfolds, *dtotal;
+    if ((rc = fold_stage(ctx, who, K, F, nsub, d_stats, &dfolds, &dtotal))) return rc;
+    if (!ctx->ard_hyper.ensure((size_t)nprob * 6 * 8) || !ctx->ard_coef.ensure((size_t)nprob * K * 8) ||
+        !ctx->ard_lambda.ensure((size_t)nprob * K * 8) || !ctx->ard_info.ensure((size_t)nprob * 6 * 8) ||
+        !ctx->ard_held.ensure((size_t)F * Q * 3 * 8))
         return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(ard path) failed");
-    double* dfolds = nfold ? (double*)ctx->lasso_sys.p : nullptr;
-    double* dtotal = (double*)ctx->lasso_sys.p + nfold * T;
     FSNAP_HIP(hipMemcpyAsync(ctx->ard_hyper.p, hyper, (size_t)nprob * 6 * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(hyper)");
-    FSNAP_HIP(fsnap::launch_lasso_folds(d_stats, (int)F, (int)nsub, (int)K, dfolds, dtotal, ctx->stream),
-              "launch fsnap_lasso_folds_k");
-    const int nblocks = (int)std::min<int64_t>(nprob, (int64_t)fsnap::ard_blocks_per_cu((int)K) * std::max(1, ctx->num_cu));
-    FSNAP_HIP(fsnap::launch_ard_path(nblocks, dfolds ? dfolds : d_stats, dtotal, (const double*)ctx->ard_hyper.p, (int)K, (int)F,
-                                     (int)Q, (int)max_iter, tol, (double*)ctx->ard_coef.p, (double*)ctx->ard_lambda.p,
-                                     (double*)ctx->ard_info.p, (double*)ctx->ard_held.p, ctx->stream),
+    FSNAP_HIP(fsnap::launch_ard_path(fold_grid(ctx, nprob, fsnap::ard_blocks_per_cu((int)K)), dfolds, dtotal,
+                                     (const double*)ctx->ard_hyper.p, (int)K, (int)F, (int)Q, (int)max_iter, tol,
+                                     (double*)ctx->ard_coef.p, (double*)ctx->ard_lambda.p, (double*)ctx->ard_info.p,
+                                     (double*)ctx->ard_held.p, ctx->stream),
               "launch fsnap_ard_path_k");
-    FSNAP_HIP(hipMemcpyAsync(coef_out, ctx->ard_coef.p, (size_t)nprob * K * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(coef)");
-    FSNAP_HIP(hipMemcpyAsync(lambda_out, ctx->ard_lambda.p, (size_t)nprob * K * 8, hipMemcpyDeviceToHost, ctx->stream),
-              "hipMemcpy(lambda)");
-    FSNAP_HIP(hipMemcpyAsync(info_out, ctx->ard_info.p, (size_t)nprob * 6 * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(info)");
-    FSNAP_HIP(hipMemcpyAsync(heldout_out, ctx->ard_held.p, (size_t)F * Q * 3 * 8, hipMemcpyDeviceToHost, ctx->stream),
-              "hipMemcpy(heldout)");
-    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    return FSNAP_OK;                                        // a failed problem is its own status 1, not the call's
+    // no scan: a failed problem is its own status 1, not the call's
+    return fold_finish(ctx,
+                       {{coef_out, ctx->ard_coef.p, (size_t)nprob * K * 8},
+                        {lambda_out, ctx->ard_lambda.p, (size_t)nprob * K * 8},
+                        {info_out, ctx->ard_info.p, (size_t)nprob * 6 * 8},
+                        {heldout_out, ctx->ard_held.p, (size_t)F * Q * 3 * 8}},
+                       nullptr, 0);
 }
 
 // ---- grouped K-fold greedy forward-selection paths on the per-fold statistics (kernel S1 of fsnap_lasso.hip, O1 of fsnap_omp.hip)
@@ -3208,14 +3232,12 @@ int fsnap_omp_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const dou
                    double* path_out, double* heldout_out, double* coef_out) {
     if (!ctx) return FSNAP_E_ARG;
     const char* who = "fsnap_omp_path";
-    if (!d_stats || !levels || !order_out || !path_out || !heldout_out || !coef_out || (nforced > 0 && !forced))
+    if (!levels || !order_out || !path_out || !heldout_out || !coef_out || (nforced > 0 && !forced))
         return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
-    if (K < 1 || K > fsnap::OMP_MAX_K) return ctx->fail(FSNAP_E_ARG, "%s: K = %lld (1 ... %d)", who, (long long)K, fsnap::OMP_MAX_K);
+    int rc = fold_check(ctx, who, K, fsnap::OMP_MAX_K, F, nsub, Q, 1, d_stats);
+    if (rc) return rc;
     if (S < 1 || S > K || S > fsnap::OMP_MAX_S)
         return ctx->fail(FSNAP_E_ARG, "%s: S = %lld (1 ... min(K, %d))", who, (long long)S, fsnap::OMP_MAX_S);
-    if (F < 1 || nsub < 1 || F > 0x3FFFFFF || nsub > 0x3FFFFFFF)
-        return ctx->fail(FSNAP_E_ARG, "%s: F = %lld, nsub = %lld", who, (long long)F, (long long)nsub);
-    if (Q < 1 || Q > 0xFFFFF) return ctx->fail(FSNAP_E_ARG, "%s: Q = %lld", who, (long long)Q);
     if (criterion != FSNAP_OMP_OMP && criterion != FSNAP_OMP_OLS) return ctx->fail(FSNAP_E_ARG, "%s: criterion = %d", who, criterion);
     for (int64_t i = 0; i < Q; ++i)
         if (levels[i] < 1 || levels[i] > S || (i > 0 && levels[i] < levels[i - 1]))
@@ -3226,39 +3248,28 @@ int fsnap_omp_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const dou
         for (int64_t k = 0; k < i && !bad; ++k) bad = forced[k] == forced[i];
         if (bad) return ctx->fail(FSNAP_E_ARG, "%s: forced[%lld] = %d is out of range or repeated", who, (long long)i, (int)forced[i]);
     }
-    if (!cand_fits(F * nsub, K))
-        return ctx->fail(FSNAP_E_ARG, "%s: %lld blocks x %lld doubles exceed FSNAP_CAT_STATS_MAX_BYTES", who, (long long)(F * nsub),
-                         (long long)FSNAP_PACKED_LEN(K));
-    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-    const int64_t T = FSNAP_PACKED_LEN(K), nprob = F + 1;
-    const int64_t nfold = nsub > 1 ? F : 0;                 // nsub = 1: the caller's blocks are the folds
-    if (!ctx->lasso_sys.ensure((size_t)(nfold + 1) * T * 8) || !ctx->omp_in.ensure((size_t)(nforced + Q) * 4) ||
-        !ctx->omp_order.ensure((size_t)nprob * S * 4) || !ctx->omp_path.ensure((size_t)nprob * S * 3 * 8) ||
-        !ctx->omp_held.ensure((size_t)F * S * 3 * 8) || !ctx->omp_coef.ensure((size_t)nprob * Q * K * 8))
+    const double *dfolds, *dtotal;
+    if ((rc = fold_stage(ctx, who, K, F, nsub, d_stats, &dfolds, &dtotal))) return rc;
+    const int64_t nprob = F + 1;
+    if (!ctx->omp_in.ensure((size_t)(nforced + Q) * 4) || !ctx->omp_order.ensure((size_t)nprob * S * 4) ||
+        !ctx->omp_path.ensure((size_t)nprob * S * 3 * 8) || !ctx->omp_held.ensure((size_t)F * S * 3 * 8) ||
+        !ctx->omp_coef.ensure((size_t)nprob * Q * K * 8))
         return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(omp path) failed");
-    double* dfolds = nfold ? (double*)ctx->lasso_sys.p : nullptr;
-    double* dtotal = (double*)ctx->lasso_sys.p + nfold * T;
     int* dforced = nforced ? (int*)ctx->omp_in.p : nullptr;
     int* dlevels = (int*)ctx->omp_in.p + nforced;
     if (nforced)
         FSNAP_HIP(hipMemcpyAsync(dforced, forced, (size_t)nforced * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(forced)");
     FSNAP_HIP(hipMemcpyAsync(dlevels, levels, (size_t)Q * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(levels)");
-    FSNAP_HIP(fsnap::launch_lasso_folds(d_stats, (int)F, (int)nsub, (int)K, dfolds, dtotal, ctx->stream),
-              "launch fsnap_lasso_folds_k");
-    const int nblocks = (int)std::min<int64_t>(nprob, (int64_t)fsnap::omp_blocks_per_cu((int)K, (int)S) * std::max(1, ctx->num_cu));
-    FSNAP_HIP(fsnap::launch_omp_path(nblocks, dfolds ? dfolds : d_stats, dtotal, (int)K, (int)F, criterion, dforced, (int)nforced,
-                                     (int)S, dlevels, (int)Q, (int*)ctx->omp_order.p, (double*)ctx->omp_path.p,
-                                     (double*)ctx->omp_held.p, (double*)ctx->omp_coef.p, ctx->stream),
+    FSNAP_HIP(fsnap::launch_omp_path(fold_grid(ctx, nprob, fsnap::omp_blocks_per_cu((int)K, (int)S)), dfolds, dtotal, (int)K,
+                                     (int)F, criterion, dforced, (int)nforced, (int)S, dlevels, (int)Q, (int*)ctx->omp_order.p,
+                                     (double*)ctx->omp_path.p, (double*)ctx->omp_held.p, (double*)ctx->omp_coef.p, ctx->stream),
               "launch fsnap_omp_path_k");
-    FSNAP_HIP(hipMemcpyAsync(order_out, ctx->omp_order.p, (size_t)nprob * S * 4, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(order)");
-    FSNAP_HIP(hipMemcpyAsync(path_out, ctx->omp_path.p, (size_t)nprob * S * 3 * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(path)");
-    FSNAP_HIP(hipMemcpyAsync(heldout_out, ctx->omp_held.p, (size_t)F * S * 3 * 8, hipMemcpyDeviceToHost, ctx->stream),
-              "hipMemcpy(heldout)");
-    FSNAP_HIP(hipMemcpyAsync(coef_out, ctx->omp_coef.p, (size_t)nprob * Q * K * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(coef)");
-    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    for (int64_t i = 0; i < nprob * Q * K; ++i)
-        if (!std::isfinite(coef_out[i])) return FSNAP_NUM_NONFINITE;
-    return FSNAP_OK;
+    return fold_finish(ctx,
+                       {{order_out, ctx->omp_order.p, (size_t)nprob * S * 4},
+                        {path_out, ctx->omp_path.p, (size_t)nprob * S * 3 * 8},
+                        {heldout_out, ctx->omp_held.p, (size_t)F * S * 3 * 8},
+                        {coef_out, ctx->omp_coef.p, (size_t)nprob * Q * K * 8}},
+                       coef_out, nprob * Q * K);
 }
 
 // ---- grouped K-fold cross-validation of weight candidates (kernels V0, V1, V2 of fsnap_cv.hip) -----------------------------

@@ -150,13 +150,13 @@ struct fsnap_ctx {
     // fsnap_ridge_path: [G | c | alphas], row classes, per-workgroup base tiles, sums, info, predictions (the unit index and
     // offsets share loco_idx / loco_off); kept between calls
     DevBuf path_in, path_cls, path_base, path_sums, path_info, path_pred;
-    // fsnap_lasso_path: [fold blocks (nsub > 1 only) | total], alphas, coefficients, info, held-out sums; kept between calls
-    DevBuf lasso_sys, lasso_alphas, lasso_coef, lasso_info, lasso_held;
-    // fsnap_ard_path: hyper-parameters, coefficients, lambdas, info, held-out sums (the fold sums live in lasso_sys); kept
-    // between calls
+    // the fold paths' shared stage (fold_stage in fsnap_capi.cpp): [fold blocks (nsub > 1 only) | total]; kept between calls
+    DevBuf fold_sys;
+    // fsnap_lasso_path: alphas, coefficients, info, held-out sums; kept between calls
+    DevBuf lasso_alphas, lasso_coef, lasso_info, lasso_held;
+    // fsnap_ard_path: hyper-parameters, coefficients, lambdas, info, held-out sums; kept between calls
     DevBuf ard_hyper, ard_coef, ard_lambda, ard_info, ard_held;
-    // fsnap_omp_path: [forced | levels], orders, path rows, held-out sums, coefficients (the fold sums live in lasso_sys); kept
-    // between calls
+    // fsnap_omp_path: [forced | levels], orders, path rows, held-out sums, coefficients; kept between calls
     DevBuf omp_in, omp_order, omp_path, omp_held, omp_coef;
     // fsnap_cv_candidates / fsnap_cv_candidate_rows: per-category totals followed by the F C blocks total - fold, scales, coefficients, info, the per-fold coefficient
     // tables of a launch (the chunk partials and sums share cand_rpart / cand_res); kept between calls

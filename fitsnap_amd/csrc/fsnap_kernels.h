@@ -283,11 +283,12 @@ hipError_t launch_ridge_path(int nblocks, const double* A, int64_t lda, int K, c
                              const double* alphas, int Q, const unsigned char* rcls, int nclass, double* Bg, double* sums,
                              double* info, double* pred, int64_t m, hipStream_t st);
 
-// Grouped K-fold LASSO alpha paths (fsnap_lasso.hip; K <= LASSO_MAX_K).  Kernel S1: folds[f] (F packed blocks of K^2 + K + 3
-// doubles; nullptr with nsub = 1, where the blocks of stats are the folds) = the sum of blocks f nsub ... f nsub + nsub - 1 of
-// stats, total = the sum of the folds, both in index order.
+// The fold sums of the grouped K-fold paths (kernel S1, in fsnap_lasso.hip; shared by the LASSO, ARD and OMP paths): folds[f]
+// (F packed blocks of K^2 + K + 3 doubles; nullptr with nsub = 1, where the blocks of stats are the folds) = the sum of blocks
+// f nsub ... f nsub + nsub - 1 of stats, total = the sum of the folds, both in index order.
+hipError_t launch_fold_sums(const double* stats, int F, int nsub, int K, double* folds, double* total, hipStream_t st);
+// Grouped K-fold LASSO alpha paths (fsnap_lasso.hip; K <= LASSO_MAX_K).
 constexpr int LASSO_MAX_K = 144;
-hipError_t launch_lasso_folds(const double* stats, int F, int nsub, int K, double* folds, double* total, hipStream_t st);
 // Kernel S2: problem p = f Q + q (f = F: no fold left out) is fsnap_lasso_gram on (total - folds[f]) with l1_reg = alphas[q] n,
 // from zeros; a coordinate j with total G_jj = 0 or downdated G_jj <= LOCO_PIVOT_TOL total G_jj is skipped.  coef[p][K],
 // info[p][4] = (sweeps, last duality gap, l1_reg, n), heldout[p][3] (p < F Q) = (n_f, bb_f - 2 beta . c_f + beta^T G_f beta, bb_f).

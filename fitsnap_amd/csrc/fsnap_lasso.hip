@@ -2,7 +2,8 @@
 // tables are solvers/lasso_path.py).  Coordinate descent touches the rows only through (X^T X, X^T y, |y|^2), so with one packed
 // block [G_f | c_f | bb_f, sum wb, n_f] per fold (fsnap_cat_normal_eq) the training system of fold f is "total minus block f"
 // and the (F + 1) x Q problems (fold f left out, or none; alpha_q) are independent K x K recurrences.
-//   Kernel S1: fold blocks (the sum of nsub sub-blocks each, in index order) and the total T (the folds in index order).
+//   Kernel S1: fold blocks (the sum of nsub sub-blocks each, in index order) and the total T (the folds in index order); the
+//              ARD and OMP paths (fsnap_ard.hip, fsnap_omp.hip) start from it too.
 //   Kernel S2: one wave per problem, grid-stride.  The downdated matrix sits in LDS as the packed lower triangle (K = 144:
 //              83 520 B; the square would not fit), H = Qm w and w in registers (lane l owns columns l, l + 64, l + 128), row
 //              i + 1 is fetched from LDS while coordinate i is updated (the row does not depend on w).  The iteration is
@@ -11,6 +12,7 @@
 // A problem's result depends on its own (fold, alpha) only: bit-identical run to run and under any permutation of the grid.
 #include <hip/hip_runtime.h>
 
+#include "fsnap_fold_body.h"
 #include "fsnap_kernels.h"
 #include "fsnap_wave_sum.h"
 
@@ -18,8 +20,8 @@ namespace fsnap {
 namespace {
 
 // Kernel S1.  grid ceil(T / 256); folds may be nullptr (nsub = 1: the blocks are the folds)
-__global__ __launch_bounds__(256) void fsnap_lasso_folds_k(const double* __restrict__ stats, int F, int nsub, int64_t T,
-                                                           double* __restrict__ folds, double* __restrict__ total) {
+__global__ __launch_bounds__(256) void fsnap_fold_sums_k(const double* __restrict__ stats, int F, int nsub, int64_t T,
+                                                         double* __restrict__ folds, double* __restrict__ total) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= T) return;
     double tot = 0.0;
@@ -33,20 +35,6 @@ __global__ __launch_bounds__(256) void fsnap_lasso_folds_k(const double* __restr
     total[e] = tot;
 }
 
-// the value of lane `src` (uniform) in every lane
-__device__ __forceinline__ double lane_bcast(double v, int src) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u & 0xFFFFFFFFull), src);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), src);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // Kernel S2.  NE = ceil(K / 64) columns per lane.  LDS: K (K + 1) / 2 + 2 K doubles (triangle, qv, beta).
 template <int NE>
 __global__ __launch_bounds__(64) void fsnap_lasso_cd_k(const double* __restrict__ folds, const double* __restrict__ total,
@@ -55,7 +43,6 @@ __global__ __launch_bounds__(64) void fsnap_lasso_cd_k(const double* __restrict_
                                                        double* __restrict__ info, double* __restrict__ heldout) {
     extern __shared__ __attribute__((aligned(16))) double lasso_lds[];
     const int lane = threadIdx.x;
-    const int64_t T = (int64_t)K * K + K + 3;
     const int KK = K * K;
     double* tri = lasso_lds;
     double* sq = tri + K * (K + 1) / 2;
@@ -70,7 +57,8 @@ __global__ __launch_bounds__(64) void fsnap_lasso_cd_k(const double* __restrict_
     }
     for (int p = blockIdx.x; p < nprob; p += gridDim.x) {
         const int f = p / Q, q = p - f * Q;
-        const double* Gf = f < F ? folds + (int64_t)f * T : nullptr;
+        const FoldView fv = fold_view(folds, total, f, F, K);
+        const double* Gf = fv.Gf;
         // the downdated lower triangle, subtracted while filling
 #pragma unroll 4
         for (int x = lane; x < KK; x += 64) {
@@ -81,12 +69,9 @@ __global__ __launch_bounds__(64) void fsnap_lasso_cd_k(const double* __restrict_
                 tri[i * (i + 1) / 2 + j] = v;
             }
         }
-        const double bb_f = Gf ? Gf[KK + K] : 0.0, n_f = Gf ? Gf[KK + K + 2] : 0.0;
-        const double y2 = Gf ? total[KK + K] - bb_f : total[KK + K];
-        const double n = Gf ? total[KK + K + 2] - n_f : total[KK + K + 2];
+        const double y2 = fv.y2, n = fv.n;
         const double l1 = alphas[q] * n;
         __syncthreads();
-        // dead coordinates: the total never touched the column, or the subtraction left noise
         unsigned long long dead[NE];
         double qv[NE], h[NE], w[NE];
 #pragma unroll
@@ -94,7 +79,7 @@ __global__ __launch_bounds__(64) void fsnap_lasso_cd_k(const double* __restrict_
             const int j = valid[e] ? col[e] : 0;
             const double tjj = total[(int64_t)j * K + j];
             const double qjj = tri[j * (j + 1) / 2 + j];
-            const bool d = valid[e] && (tjj == 0.0 || qjj <= pivot_tol * tjj);
+            const bool d = valid[e] && fold_dead(tjj, qjj, pivot_tol);
             dead[e] = __ballot(d);
             double v = 0.0;
             if (valid[e] && !d) v = Gf ? total[KK + j] - Gf[KK + j] : total[KK + j];
@@ -222,12 +207,8 @@ __global__ __launch_bounds__(64) void fsnap_lasso_cd_k(const double* __restrict_
             }
             s1 = wave_sum(s1);
             s2 = wave_sum(s2);
-            if (lane == 0) {
-                double* ho = heldout + (int64_t)p * 3;         // p = f Q + q for f < F
-                ho[0] = n_f;
-                ho[1] = bb_f - 2.0 * s1 + s2;
-                ho[2] = bb_f;
-            }
+            // p = f Q + q for f < F
+            if (lane == 0) fold_heldout_store(heldout + (int64_t)p * 3, fv.n_f, fv.bb_f - 2.0 * s1 + s2, fv.bb_f);
         }
         __syncthreads();                                       // the next problem refills the triangle
     }
@@ -242,9 +223,9 @@ int lasso_blocks_per_cu(int K) {
     return per < 1 ? 1 : per > 8 ? 8 : (int)per;
 }
 
-hipError_t launch_lasso_folds(const double* stats, int F, int nsub, int K, double* folds, double* total, hipStream_t st) {
+hipError_t launch_fold_sums(const double* stats, int F, int nsub, int K, double* folds, double* total, hipStream_t st) {
     const int64_t T = (int64_t)K * K + K + 3;
-    fsnap_lasso_folds_k<<<dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st>>>(stats, F, nsub, T, folds, total);
+    fsnap_fold_sums_k<<<dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st>>>(stats, F, nsub, T, folds, total);
     return hipGetLastError();
 }
 

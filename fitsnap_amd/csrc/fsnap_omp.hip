@@ -14,6 +14,7 @@
 // A problem's result depends on its own fold only: bit-identical run to run and under any permutation or subset of the folds.
 #include <hip/hip_runtime.h>
 
+#include "fsnap_fold_body.h"
 #include "fsnap_kernels.h"
 #include "fsnap_wave_sum.h"
 
@@ -21,14 +22,6 @@ namespace fsnap {
 namespace {
 
 constexpr int OMP_CRIT_OLS = 1;
-
-// the value of lane `src` (uniform) in every lane
-__device__ __forceinline__ double omp_bcast(double v, int src) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u & 0xFFFFFFFFull), src);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), src);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
 
 // a[slot] for a uniform slot without indexing the registers dynamically
 template <typename V, int NE>
@@ -67,6 +60,8 @@ __global__ __launch_bounds__(64) void fsnap_omp_path_k(const double* __restrict_
         cidx[e] = valid[e] ? col[e] : 0;
     }
     for (int f = blockIdx.x; f <= F; f += gridDim.x) {
+        // (fold_view's statements, kept as this kernel's own text: through the shared view the register allocation of O1
+        // comes out differently -- two scalar registers fewer spilled --, and the shared pieces are to cost or change nothing)
         const double* Gf = f < F ? folds + (int64_t)f * T : nullptr;
         const double bb_f = Gf ? Gf[KK + K] : 0.0, n_f = Gf ? Gf[KK + K + 2] : 0.0;
         double e_cur = Gf ? total[KK + K] - bb_f : total[KK + K];
@@ -77,8 +72,7 @@ __global__ __launch_bounds__(64) void fsnap_omp_path_k(const double* __restrict_
             const int j = cidx[e];
             const double tjj = total[(int64_t)j * K + j];
             const double qjj = Gf ? tjj - Gf[(int64_t)j * K + j] : tjj;
-            // dead: the total never touched the column, or the subtraction left noise
-            alive[e] = valid[e] && !(tjj == 0.0 || qjj <= pivot_tol * tjj);
+            alive[e] = valid[e] && !fold_dead(tjj, qjj, pivot_tol);
             cand[e] = alive[e];
             qd[e] = alive[e] ? qjj : 0.0;
             t[e] = qd[e];
@@ -132,9 +126,9 @@ __global__ __launch_bounds__(64) void fsnap_omp_path_k(const double* __restrict_
             }
             if (js >= 0) {
                 const int ol = js & 63, oe = js >> 6;
-                const double tj = omp_bcast(omp_pick(t, oe), ol);
-                const double rj = omp_bcast(omp_pick(r, oe), ol);
-                const double qj = omp_bcast(omp_pick(qd, oe), ol);
+                const double tj = lane_bcast(omp_pick(t, oe), ol);
+                const double rj = lane_bcast(omp_pick(r, oe), ol);
+                const double qj = lane_bcast(omp_pick(qd, oe), ol);
                 const double l = sqrt(tj);
                 const double z = rj / l;
                 sc_out = rj * rj / (criterion == OMP_CRIT_OLS ? tj : qj);
@@ -177,7 +171,7 @@ __global__ __launch_bounds__(64) void fsnap_omp_path_k(const double* __restrict_
                 for (int i = 0; i < 2; ++i) x[i] = lane + 64 * i < ns ? sz[lane + 64 * i] : 0.0;
                 for (int v = ns - 1; v >= 0; --v) {
                     const int jv = so[v];
-                    const double bv = omp_bcast(v < 64 ? x[0] : x[1], v & 63) / W[(size_t)v * KP + jv];
+                    const double bv = lane_bcast(v < 64 ? x[0] : x[1], v & 63) / W[(size_t)v * KP + jv];
 #pragma unroll
                     for (int i = 0; i < 2; ++i) {
                         const int p = lane + 64 * i;
@@ -225,11 +219,7 @@ __global__ __launch_bounds__(64) void fsnap_omp_path_k(const double* __restrict_
                 path[at * 3 + 0] = e_cur;
                 path[at * 3 + 1] = sc_out;
                 path[at * 3 + 2] = pv_out;
-                if (Gf) {
-                    heldout[at * 3 + 0] = n_f;
-                    heldout[at * 3 + 1] = h_last;
-                    heldout[at * 3 + 2] = bb_f;
-                }
+                if (Gf) fold_heldout_store(heldout + at * 3, n_f, h_last, bb_f);
             }
             if (qi < Q && levels[qi] == s + 1) {
                 // the dense coefficient row through LDS, so that every global entry is written once

@@ -1,5 +1,5 @@
-// fsnap_wave_sum.h — wave reductions of the post-fit kernels, each in a fixed order: the order is part of every kernel's
-// bit-identity promise.  (Kept out of fsnap_device_common.h: the recorded PMC traffic of the SYRK kernels,
+// fsnap_wave_sum.h — wave reductions (and the lane broadcast) of the post-fit kernels, each in a fixed order: the order is part
+// of every kernel's bit-identity promise.  (Kept out of fsnap_device_common.h: the recorded PMC traffic of the SYRK kernels,
 // profiles/pmc_traffic.json, is keyed on that file's digest.)  Internal.
 #pragma once
 #include "fsnap_device_common.h"
@@ -20,4 +20,17 @@ __device__ __forceinline__ double wave_sum(double v) {
 __device__ __forceinline__ double wave_sum_desc(double v) {
     for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+// maximum over the 64 lanes of a wave
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+// the value of lane `src` (uniform) in every lane
+__device__ __forceinline__ double lane_bcast(double v, int src) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u & 0xFFFFFFFFull), src);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), src);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }

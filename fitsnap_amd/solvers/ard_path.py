@@ -3,7 +3,7 @@
 
 Every iteration of ``ARD._ard_loop`` touches the weighted training rows only through (X^T X, X^T y, |y|^2, sum y, n).  With
 the units dealt into F folds and one packed block [G_f | c_f | bb_f, sum wb_f, n_f] per fold -- ONE pass over the rows, the
-layout and statistics of ``lasso_path`` --, problem (f, q) is the ARD fit of setting q on "total minus block f" (f = F: on all
+layout and statistics of the fold frame --, problem (f, q) is the ARD fit of setting q on "total minus block f" (f = F: on all
 training rows):
 
     Qm = T.G - G_f,  qv = T.c - c_f,  y2 = T.bb - bb_f,  s = T.sum wb - sum wb_f,  n = T.n - n_f
@@ -23,20 +23,17 @@ var <= 0 gets status 1 without being run.
 The GPU pass is ``fsnap_ard_path`` (csrc/fsnap_ard.hip, K <= 144, one workgroup per problem); this module holds the grid, the
 hyper-parameters, the same scheme on the host (``ard_path_host``: ``ARD._ard_loop`` over the same downdated systems -- the
 route of wider systems, the baseline and the check of the kernel; no GPU needed once the statistics are given) and the
-picks.  Fold dealing, block sums, downdates and tables are ``lasso_path``'s.
+picks.  Fold dealing, block sums, downdates and tables are the fold frame's (``folds``; DESIGN.md, "The fold frame").
 """
 from __future__ import annotations
 
-import os
 from collections import namedtuple
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import loco, ridge_path
+from . import folds as fold_frame, ridge_path
 from .._hostblas import blas_threads
-from .lasso_path import (CAT_STATS_MAX_BYTES, HOST_THREADS, ROWS_TABLE_MAX, TABLES, cv_curve, deal_folds, downdated, pool_rows,
-                         row_categories, stats_table, sum_blocks, unpack)
+from .folds import TABLES, cv_curve, downdated, download_blocks, stats_table, sum_blocks, unpack
 
 MAX_K = 144                  # fsnap::ARD_MAX_K
 METHODS = ("auto", "device", "host")
@@ -187,16 +184,10 @@ def ard_path_host(blocks, K, hyper, max_iter, tol, nsub=1, threads=None, run=Non
         if f < F:
             held[f, q, 1] = bb - 2.0 * (beta @ c) + beta @ (G @ beta)
 
-    threads = min(HOST_THREADS, os.cpu_count() or 1) if threads is None else int(threads)
     # one limit of the BLAS pools around all problems: the loop's own limits then nest inside it, and whatever order the
     # threads leave theirs in, the pools get their size back here
     with blas_threads(K):
-        if threads > 1 and (F + 1) * Q > 1:
-            with ThreadPoolExecutor(max_workers=threads) as pool:
-                list(pool.map(solve, range((F + 1) * Q)))
-        else:
-            for p in range((F + 1) * Q):
-                solve(p)
+        fold_frame.run_pool(solve, (F + 1) * Q, threads)
     return coef, lam, info, held
 
 
@@ -223,7 +214,7 @@ def pick(cv_error, cv_se, nonzeros):
 
 def cv_picks(heldout, status, nonzeros):
     """(cv_error, cv_se, best, sparsest) from heldout (F x Q x 3), status ((F + 1) x Q) and the non-zero counts of the all-rows
-    fits: ``lasso_path.cv_curve``'s pooled error and standard error, NaN for a setting with a status-1 problem, and ``pick``."""
+    fits: ``folds.cv_curve``'s pooled error and standard error, NaN for a setting with a status-1 problem, and ``pick``."""
     Q = heldout.shape[1]
     cv_error, cv_se, _, _ = cv_curve(np.arange(Q, dtype=np.float64), heldout)
     failed = (np.asarray(status) == 1).any(axis=0)
@@ -233,28 +224,15 @@ def cv_picks(heldout, status, nonzeros):
 
 
 def setting_index(frame):
-    """A ``lasso_path`` table keyed by the position in the grid: index (setting, Row_Type)."""
+    """A fold-frame table keyed by the position in the grid: index (setting, Row_Type)."""
     frame.index = frame.index.set_levels(frame.index.levels[0].astype(np.int64), level=0).set_names(["setting", "Row_Type"])
     return frame
-
-
-def download_blocks(ctx, dptr, ncat, K):
-    """The ``ncat`` packed blocks at the device address ``dptr`` as rows of an array."""
-    T = K * K + K + 3
-    blocks = np.empty((ncat, T))
-    for i in range(ncat):
-        G, c, s = ctx.download_packed(dptr + i * T * 8, K)
-        blocks[i, :K * K], blocks[i, K * K:K * K + K], blocks[i, K * K + K:] = G.ravel(), c, s
-    return blocks
 
 
 def ard_path(solver, grid, folds=5, by="Configs", fs_dict=None, b=None, w=None, tol=None, max_iter=None, method="auto",
              table="auto", seed=0):
     """``Solver.ard_path``: see there."""
-    from .. import _capi
-
     who = "ard_path"
-    pt = solver.pt
     check_solver(solver)                                    # every rank refuses alike
     section = solver.config.sections["ARD"]
     direct = bool(section.directmethod)
@@ -263,52 +241,22 @@ def ard_path(solver, grid, folds=5, by="Configs", fs_dict=None, b=None, w=None, 
         raise ValueError(f"ard_path: method must be one of {', '.join(METHODS)}")
     if table not in TABLES:
         raise ValueError(f"ard_path: table must be one of {', '.join(TABLES)}")
-    fitted = np.array([1.0 if solver.last_statistics is not None else 0.0])
-    if pt.multi:
-        pt.allreduce_host(fitted, _capi.REDUCE_MAX)
-    if not fitted[0]:
-        raise RuntimeError("ard_path: call perform_fit first")
+    fold_frame.check_fitted(solver, who)
     tol = float(type(solver).TOL if tol is None else tol)
     max_iter = int(type(solver).MAX_ITER if max_iter is None else max_iter)
     if not (np.isfinite(tol) and tol >= 0.0) or max_iter < 1:
         raise ValueError(f"ard_path: tol = {tol}, max_iter = {max_iter}")
-    # b and w are checked for their lengths only: the statistics and the row pass read the resident rows, truths and weights
-    labels, b, w, testing, names, row_class, nclass = ridge_path.resolve_rows(solver, who, by, fs_dict, b, w)
-    m, train = b.shape[0], ~testing
-    ctx = pt.hip()
-    K = ctx.K if m > 0 else 0
-    if pt.multi:
-        K = max(pt.allgather_object(int(K)))
-    if m > 0 and ctx.m != m:
-        raise ValueError(f"ard_path: the resident rows ({ctx.m} x {ctx.K}) are not those of the fit ({m} rows)")
+    fr = fold_frame.resolve(solver, who, by, fs_dict, b, w)
+    K, Q = fr.K, len(grid)
     method = choose_method(method, K)
-    _, _, units = loco.unit_index(labels[by], train)
-    if pt.multi:
-        units = [u for part in pt.allgather_object(units) for u in part]      # a unit may span ranks
-    fold_of_unit, F = deal_folds(units, folds, seed)
-    Q = len(grid)
-    asked = table
-    if table == "auto":
-        table = "rows" if F * Q <= ROWS_TABLE_MAX else "stats"
-    # ONE layout, fold x row class, serves the statistics and the row pass (lasso_path's scheme)
-    nsub = nclass if F * nclass * (K * K + K + 3) * 8 <= CAT_STATS_MAX_BYTES else 1
-    if nsub == 1 and nclass > 1:
-        if asked == "rows":
-            raise ValueError(f"ard_path: table='rows' needs {F} folds x {nclass} row classes of statistics, more than "
-                             "FSNAP_CAT_STATS_MAX_BYTES; use table='stats'")
-        table = "stats"
-    ncat = F * nsub
-    cat = row_categories(labels[by], train, fold_of_unit, row_class, nsub)
-    layout = ctx.cat_prepare(cat, ncat) if m > 0 else 0
-    if pt.multi:
-        layout, dptr = ctx.cat_normal_eq_dist(layout, K, ncat)
-    else:
-        dptr = ctx.cat_normal_eq(layout)
+    fold_of_unit, F = fold_frame.deal_units(fr.pt, fr.labels, fr.train, folds, seed)
+    table, nsub = fold_frame.plan_table(who, table, F, Q, fr.nclass, K)
+    fold_frame.statistics(fr, fold_of_unit, F, nsub)
     # the scalars (bb, sum wb, n) of the blocks decide the hyper-parameters of every problem, on either route
-    blocks = download_blocks(ctx, dptr, ncat, K)
+    blocks = download_blocks(fr.ctx, fr.dptr, fr.ncat, K)
     hyper, run = fold_hypers(*sum_blocks(blocks, nsub), K, grid, direct)
     if method == "device":
-        coef, lam, info, held = ctx.ard_path(dptr, K, F, nsub, hyper, max_iter, tol)
+        coef, lam, info, held = fr.ctx.ard_path(fr.dptr, K, F, nsub, hyper, max_iter, tol)
     else:
         coef, lam, info, held = ard_path_host(blocks, K, hyper, max_iter, tol, nsub, run=run)
     void_problems(run, coef, lam, info, held)
@@ -318,18 +266,10 @@ def ard_path(solver, grid, folds=5, by="Configs", fs_dict=None, b=None, w=None, 
     cv_error, cv_se, best, sparsest = cv_picks(held, status, nonzeros)
     index = np.arange(Q, dtype=np.float64)
     if table == "rows":
-        if m > 0:
-            # a failed refit's NaN vector would poison its rows' sums only; they are reported as they come
-            sums4 = ctx.candidate_rows(layout, np.nan_to_num(coef[:F]).reshape(F * Q, K), None, _capi.CAND_ERROR_SUMS, ncat)
-            counts = np.bincount(cat[cat >= 0], minlength=ncat)
-            pooled = pool_rows(sums4, counts, F, Q, nclass)
-        else:
-            pooled = np.zeros((Q, nclass, 4))
-        if pt.multi:
-            pooled = np.ascontiguousarray(pooled)
-            pt.allreduce_host(pooled.reshape(-1))
+        # a failed refit's NaN vector would poison its rows' sums only; they are reported as they come
+        pooled = fold_frame.rows_pooled(fr, np.nan_to_num(coef[:F]), F, Q)
         pooled[(status == 1).any(axis=0), :, 1:] = np.nan
-        frame = ridge_path.path_table(index, pooled, names)
+        frame = ridge_path.path_table(index, pooled, fr.names)
     else:
         frame = stats_table(index, held)
     return ArdPath(grid, fits, lam[F].copy(), nonzeros, info[:, :, 0].astype(np.int64), status, info[:, :, 2].copy(),

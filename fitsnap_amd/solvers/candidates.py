@@ -233,7 +233,7 @@ class CandidateFits:
     def cross_validate(self, S, folds=5, by="Configs", seed=0, method="auto"):
         """Grouped K-fold cross-validation of the candidates S (P x ncat): the units ``fs_dict[by]`` of the training rows
         are dealt into folds (``folds``: an int F, ``None`` for one fold per unit, or a mapping unit -> fold; ``seed`` as in
-        ``lasso_path.deal_folds``), every candidate is refitted with each fold left out, and every training row is scored
+        ``folds.deal_folds``), every candidate is refitted with each fold left out, and every training row is scored
         under the refit that did not see its unit.  Returns a ``CandidateCV`` (solvers/candidates_cv.py): ``coef`` (P, F, K),
         ``status``, ``min_pivot``, ``route``, ``fold_of_unit``, pooled ``sums`` (P, ncat, 5), ``tables()``,
         ``row_type_errors`` and ``cost(weights, metric)`` -- the weight search's objective on held-out rows.

@@ -1,7 +1,7 @@
 """Grouped K-fold cross-validation of the weight candidates of ``CandidateFits`` (``CandidateFits.cross_validate``).
 
 The weight search scores a candidate by its errors on the rows it was fitted to.  Here the units (configurations) are dealt into
-F folds (``lasso_path.deal_folds``), every candidate is refitted F times with one fold left out, and every row is scored under
+F folds (``folds.deal_folds``), every candidate is refitted F times with one fold left out, and every row is scored under
 the refit that did not see its unit.  With one packed block of statistics per (fold, category) -- ONE pass over the rows,
 ``fsnap_cat_prepare`` + ``fsnap_cat_normal_eq`` with the composite category fold * C + c -- the refit (p, f) is
 
@@ -15,7 +15,7 @@ from __future__ import annotations
 import numpy as np
 
 from .. import _capi
-from . import lasso_path, loco
+from . import folds as fold_frame
 
 MAX_K = 144                  # fsnap::CV_MAX_K
 METHODS = ("auto", "device", "composed")
@@ -176,24 +176,21 @@ def fold_key(folds, by, seed):
 
 def composite_layout(cf, folds, by, seed):
     """(composite categories per row, fold_of_unit, F) of the CandidateFits ``cf``: units from ``fs_dict[by]`` over the
-    training rows, folds from ``lasso_path.deal_folds`` (collective: a unit gets one fold on every rank)."""
+    training rows, folds from ``folds.deal_units`` (collective: a unit gets one fold on every rank)."""
     if by not in cf.fs_dict:
         raise KeyError(f"cross_validate: fs_dict has no {by!r} labels to take the units from")
     labels = cf.fs_dict[by]
     if len(labels) != cf.m:
         raise ValueError(f"cross_validate: fs_dict[{by!r}] must have one entry per row")
     train = ~cf.testing
-    _, _, units = loco.unit_index(labels, train)
-    if cf.pt.multi:
-        units = [u for part in cf.pt.allgather_object(units) for u in part]
-    fold_of_unit, F = lasso_path.deal_folds(units, folds, seed)
+    fold_of_unit, F = fold_frame.deal_units(cf.pt, labels, train, folds, seed)
     if F < 2:
         raise ValueError(f"cross_validate: {F} fold; at least 2 are needed to hold rows out")
     K, C = cf.K, cf.ncat
-    if F * C * (K * K + K + 3) * 8 > lasso_path.CAT_STATS_MAX_BYTES:
+    if F * C * (K * K + K + 3) * 8 > fold_frame.CAT_STATS_MAX_BYTES:
         raise ValueError(f"cross_validate: {F} folds x {C} categories of statistics of order {K} exceed "
                          "FSNAP_CAT_STATS_MAX_BYTES; use fewer folds")
-    fold = lasso_path.row_categories(labels, train, fold_of_unit, None, 1)
+    fold = fold_frame.row_categories(labels, train, fold_of_unit, None, 1)
     ccat = np.where((fold >= 0) & (cf.cat >= 0), fold * C + cf.cat, -1).astype(np.int32)
     return ccat, fold_of_unit, F
 

@@ -2,7 +2,7 @@
 
 "The best s of my K basis functions, and which s": forward selection hands out a nested, ordered list of columns with the
 UNSHRUNK least-squares fit at every size.  It touches the weighted training rows only through (X^T X, X^T y, |y|^2), so with
-the units dealt into F folds and one packed block per fold -- ``lasso_path``'s ONE pass over the rows, category = fold x row
+the units dealt into F folds and one packed block per fold -- the fold frame's ONE pass over the rows, category = fold x row
 class -- the training system of fold f is "total minus block f":
 
     Qm = T.G - G_f,  qv = T.c - c_f,  y2 = T.bb - bb_f                                  (f = F: the total alone)
@@ -22,19 +22,17 @@ criterion, with the right-hand side carried along (``fsnap_omp_gram``, include/f
 column that lowers the residual most).  The GPU pass is ``fsnap_omp_path`` (csrc/fsnap_omp.hip, K <= 144, at most 128 steps,
 one wave per problem); this module holds the same scheme on the host (``omp_path_host``: ``_capi.omp_gram`` over the same
 downdated systems -- the route of wider systems, the baseline and the check of the kernel; no GPU needed once the statistics
-are given), the picks and the tables.  Fold dealing, block sums, downdates and tables are ``lasso_path``'s.
+are given), the picks and the tables.  Fold dealing, block sums, downdates and tables are the fold frame's (``folds``;
+DESIGN.md, "The fold frame").
 """
 from __future__ import annotations
 
-import os
 from collections import namedtuple
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import loco, ridge_path
-from .lasso_path import (CAT_STATS_MAX_BYTES, HOST_THREADS, METHODS, ROWS_TABLE_MAX, TABLES, cv_curve, deal_folds, downdated,
-                         pool_rows, row_categories, sum_blocks, unpack)
+from . import folds as fold_frame, ridge_path
+from .folds import METHODS, TABLES, cv_curve, downdated, download_blocks, sum_blocks, unpack
 
 MAX_K = 144                  # fsnap::OMP_MAX_K
 MAX_STEPS = 128              # fsnap::OMP_MAX_S: the factor rows of a problem stay in one CU's LDS
@@ -133,18 +131,12 @@ def omp_path_host(blocks, K, criterion, forced, S, levels, nsub=1, threads=None)
             held[f, :, 0], held[f, :, 2] = nf, bb
             held[f, :, 1] = bb - 2.0 * (beta @ c) + np.einsum("sk,sk->s", beta @ G, beta)
 
-    threads = min(HOST_THREADS, os.cpu_count() or 1) if threads is None else int(threads)
-    if threads > 1 and F > 0:
-        with ThreadPoolExecutor(max_workers=threads) as pool:
-            list(pool.map(solve, range(F + 1)))
-    else:
-        for f in range(F + 1):
-            solve(f)
+    fold_frame.run_pool(solve, F + 1, threads)
     return order, path, held, coef
 
 
 def cv_picks(terms, heldout):
-    """(cv_error, cv_se, best, sparsest) over every step from heldout (F x S x 3): ``lasso_path.cv_curve`` with the sizes
+    """(cv_error, cv_se, best, sparsest) over every step from heldout (F x S x 3): ``folds.cv_curve`` with the sizes
     counted downwards, so that ``best`` is the smallest pooled held-out error with ties to FEWER terms and ``sparsest`` the
     fewest terms within one standard error of it.  Indices into ``terms``; both None when no fold holds rows."""
     return cv_curve(-np.asarray(terms, dtype=np.float64), heldout)
@@ -171,90 +163,43 @@ def keyed_by_terms(frame):
 def stats_table(levels, heldout):
     """``table="stats"``: DataFrame indexed (terms, Row_Type) with the ``*ALL`` row alone; ncount and w_rmse from the
     statistics form of the held-out error at the levels, mae and rmse (which need the rows) NaN."""
-    from .lasso_path import stats_table as lasso_stats_table
-
     levels = np.asarray(levels, dtype=np.int64)
-    return keyed_by_terms(lasso_stats_table(levels.astype(np.float64), np.asarray(heldout)[:, levels - 1]))
+    return keyed_by_terms(fold_frame.stats_table(levels.astype(np.float64), np.asarray(heldout)[:, levels - 1]))
 
 
 def omp_path(solver, max_terms, levels=None, criterion="ols", forced=(), folds=5, by="Configs", fs_dict=None, b=None, w=None,
              method="auto", table="auto", seed=0):
     """``Solver.omp_path``: see there."""
-    from .. import _capi
-
     who = "omp_path"
-    pt = solver.pt
     check_solver(solver)                                    # every rank refuses alike
     criterion = check_criterion(criterion)
     if method not in METHODS:
         raise ValueError(f"omp_path: method must be one of {', '.join(METHODS)}")
     if table not in TABLES:
         raise ValueError(f"omp_path: table must be one of {', '.join(TABLES)}")
-    fitted = np.array([1.0 if solver.last_statistics is not None else 0.0])
-    if pt.multi:
-        pt.allreduce_host(fitted, _capi.REDUCE_MAX)
-    if not fitted[0]:
-        raise RuntimeError("omp_path: call perform_fit first")
-    # b and w are checked for their lengths only: the statistics and the row pass read the resident rows, truths and weights
-    labels, b, w, testing, names, row_class, nclass = ridge_path.resolve_rows(solver, who, by, fs_dict, b, w)
-    m, train = b.shape[0], ~testing
-    ctx = pt.hip()
-    K = ctx.K if m > 0 else 0
-    if pt.multi:
-        K = max(pt.allgather_object(int(K)))
-    if m > 0 and ctx.m != m:
-        raise ValueError(f"omp_path: the resident rows ({ctx.m} x {ctx.K}) are not those of the fit ({m} rows)")
+    fold_frame.check_fitted(solver, who)
+    fr = fold_frame.resolve(solver, who, by, fs_dict, b, w)
+    K = fr.K
     if isinstance(max_terms, bool) or int(max_terms) != max_terms or not 1 <= int(max_terms) <= K:
         raise ValueError(f"omp_path: max_terms = {max_terms} (1 ... K = {K})")
     S = int(max_terms)
     levels = check_levels(levels, S)
     forced = check_forced(forced, K)
-    _, _, units = loco.unit_index(labels[by], train)
-    if pt.multi:
-        units = [u for part in pt.allgather_object(units) for u in part]      # a unit may span ranks
-    fold_of_unit, F = deal_folds(units, folds, seed)
+    fold_of_unit, F = fold_frame.deal_units(fr.pt, fr.labels, fr.train, folds, seed)
     method = choose_method(method, K, S)
     Q = levels.size
-    asked = table
-    if table == "auto":
-        table = "rows" if F * Q <= ROWS_TABLE_MAX else "stats"
-    # ONE layout, fold x row class, serves the statistics and the row pass (lasso_path's scheme)
-    nsub = nclass if F * nclass * (K * K + K + 3) * 8 <= CAT_STATS_MAX_BYTES else 1
-    if nsub == 1 and nclass > 1:
-        if asked == "rows":
-            raise ValueError(f"omp_path: table='rows' needs {F} folds x {nclass} row classes of statistics, more than "
-                             "FSNAP_CAT_STATS_MAX_BYTES; use table='stats'")
-        table = "stats"
-    ncat = F * nsub
-    cat = row_categories(labels[by], train, fold_of_unit, row_class, nsub)
-    # one pass over the rows: the statistics of every (fold, row class), on every rank
-    layout = ctx.cat_prepare(cat, ncat) if m > 0 else 0
-    if pt.multi:
-        layout, dptr = ctx.cat_normal_eq_dist(layout, K, ncat)
-    else:
-        dptr = ctx.cat_normal_eq(layout)
+    table, nsub = fold_frame.plan_table(who, table, F, Q, fr.nclass, K)
+    fold_frame.statistics(fr, fold_of_unit, F, nsub)
     if method == "device":
-        order, path, held, coef = ctx.omp_path(dptr, K, F, nsub, criterion, forced, S, levels)
+        order, path, held, coef = fr.ctx.omp_path(fr.dptr, K, F, nsub, criterion, forced, S, levels)
     else:
-        T = K * K + K + 3
-        blocks = np.empty((ncat, T))
-        for i in range(ncat):
-            G, c, s = ctx.download_packed(dptr + i * T * 8, K)
-            blocks[i, :K * K], blocks[i, K * K:K * K + K], blocks[i, K * K + K:] = G.ravel(), c, s
+        blocks = download_blocks(fr.ctx, fr.dptr, fr.ncat, K)
         order, path, held, coef = omp_path_host(blocks, K, criterion, forced, S, levels, nsub)
     terms = np.arange(1, S + 1)
     cv_error, cv_se, best, sparsest = cv_picks(terms, held)
     if table == "rows":
-        if m > 0:
-            sums4 = ctx.candidate_rows(layout, coef[:F].reshape(F * Q, K), None, _capi.CAND_ERROR_SUMS, ncat)
-            counts = np.bincount(cat[cat >= 0], minlength=ncat)
-            pooled = pool_rows(sums4, counts, F, Q, nclass)
-        else:
-            pooled = np.zeros((Q, nclass, 4))
-        if pt.multi:
-            pooled = np.ascontiguousarray(pooled)
-            pt.allreduce_host(pooled.reshape(-1))
-        frame = keyed_by_terms(ridge_path.path_table(levels.astype(np.float64), pooled, names))
+        pooled = fold_frame.rows_pooled(fr, coef[:F], F, Q)
+        frame = keyed_by_terms(ridge_path.path_table(levels.astype(np.float64), pooled, fr.names))
     else:
         frame = stats_table(levels, held)
     best_terms = None if best is None else int(terms[best])
