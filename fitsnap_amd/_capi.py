@@ -133,6 +133,9 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p, c_void_p]),
     "fsnap_cv_candidates_grad_rhs": (c_int, [c_void_p, c_int64, c_void_p]),
     "fsnap_cv_candidates_grad_times": (c_int, [c_void_p, c_void_p]),
+    "fsnap_candidates_evidence": (c_int, [c_void_p, c_int64, c_double, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
+                                          c_void_p]),
+    "fsnap_candidates_evidence_times": (c_int, [c_void_p, c_void_p]),
     "fsnap_row_variance": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "fsnap_row_variance_device": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
@@ -913,6 +916,31 @@ class HipContext:
         g = np.empty((int(P), int(F), int(K)))
         self._check(self._lib.fsnap_cv_candidates_grad_rhs(self._h, g.size, _ptr(g)))
         return g
+
+    def candidates_evidence(self, layout: int, alpha: float, S, active, K: int):
+        """The per-candidate solves and per-category terms of the evidence (``fsnap_candidates_evidence``, K <= 144): S and
+        active (P, ncat).  Returns (beta (P, K), info (P, 6): status, smallest scaled pivot, live columns, log|H|, tr(H^-1), 0,
+        terms (P, ncat, 2): tr(H^-1 G_c) and bb_c - 2 beta . r_c + beta' G_c beta)."""
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        active = np.ascontiguousarray(active, dtype=np.uint8)
+        if S.ndim != 2 or active.shape != S.shape:
+            raise ValueError("S and active must both be (P, ncat)")
+        P, ncat = S.shape
+        K = int(K)
+        beta = np.empty((P, max(K, 0)))
+        info = np.empty((P, 6))
+        terms = np.empty((P, ncat, 2))
+        self._check(self._lib.fsnap_candidates_evidence(
+            self._h, int(layout), float(alpha), _ptr(S) if S.size else None, int(P), int(ncat), K,
+            _ptr(active) if active.size else None, _ptr(beta) if beta.size else None, _ptr(info) if info.size else None,
+            _ptr(terms) if terms.size else None))
+        return beta, info, terms
+
+    def candidates_evidence_times(self):
+        """(E1, E2 + E3) device milliseconds of the last ``candidates_evidence`` call."""
+        ms = np.empty(2)
+        self._check(self._lib.fsnap_candidates_evidence_times(self._h, _ptr(ms)))
+        return ms
 
     # -- row-space least squares --------------------------------------------------------
     def row_variance(self, M, mode=UQ_QUAD, beta=None, scale=None, cat=None, ncat=0, want_var=True, want_preds=False):

@@ -855,6 +855,8 @@ int fsnap_ctx_destroy(fsnap_ctx* ctx) {
     if (ctx->chol_ev) (void)hipEventDestroy(ctx->chol_ev);
     for (auto& ev : ctx->cvg_ev)
         if (ev) (void)hipEventDestroy(ev);
+    for (auto& ev : ctx->evd_ev)
+        if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : ctx->ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto& sl : ctx->ring)
@@ -3484,6 +3486,84 @@ int fsnap_cv_candidates_grad_rhs(fsnap_ctx* ctx, int64_t n, double* g_out) {
     FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
     FSNAP_HIP(hipMemcpyAsync(g_out, ctx->cvg_g.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(g)");
     FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    return FSNAP_OK;
+}
+
+// ---- marginal likelihood of the candidates from the per-category statistics (kernels E1, E2, E3 of fsnap_evidence.hip) --------
+
+int fsnap_candidates_evidence(fsnap_ctx* ctx, int64_t layout, double alpha, const double* S, int P, int ncat, int64_t K,
+                              const uint8_t* active, double* beta_out, double* info_out, double* terms_out) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_candidates_evidence";
+    if (!S || P <= 0 || !active || !beta_out || !info_out || !terms_out) return ctx->fail(FSNAP_E_ARG, "%s: bad argument", who);
+    if (layout <= 0 || layout != ctx->cand_layout || ctx->cand_stats_K <= 0 || !ctx->cand_stats.p)
+        return ctx->fail(FSNAP_E_STATE, "%s: no per-category statistics of layout %lld on the context (fsnap_cat_prepare + "
+                                        "fsnap_cat_normal_eq first)", who, (long long)layout);
+    if (ncat != ctx->cand_ncat || K != ctx->cand_stats_K)
+        return ctx->fail(FSNAP_E_ARG, "%s: ncat = %d, K = %lld but the statistics have %d, %lld", who, ncat, (long long)K,
+                         ctx->cand_ncat, (long long)ctx->cand_stats_K);
+    if (K < 1 || K > fsnap::CV_MAX_K) return ctx->fail(FSNAP_E_ARG, "%s: K = %lld (1 ... %d)", who, (long long)K, fsnap::CV_MAX_K);
+    if (!std::isfinite(alpha) || alpha < 0.0) return ctx->fail(FSNAP_E_ARG, "%s: alpha = %g is negative or not finite", who, alpha);
+    const int C = ncat;
+    const int64_t T = FSNAP_PACKED_LEN(K), PT = ((int64_t)P + 7) / 8, CT = ((int64_t)C + 15) / 16;
+    const int64_t ns = fsnap::evidence_slices((int)K), npart = CT * PT * ns * 256, ntab = PT * T * 16;
+    if (!cand_fits(P, K) || (double)ntab * 8.0 > (double)FSNAP_CAT_STATS_MAX_BYTES ||
+        (double)npart * 8.0 > (double)FSNAP_CAT_STATS_MAX_BYTES || PT > 65535)
+        return ctx->fail(FSNAP_E_ARG, "%s: %d candidates x %lld doubles (the tables or the slice partials) exceed "
+                                      "FSNAP_CAT_STATS_MAX_BYTES", who, P, (long long)T);
+    for (int64_t i = 0; i < (int64_t)P * C; ++i)
+        if (!std::isfinite(S[i]))
+            return ctx->fail(FSNAP_E_ARG, "%s: S[%lld][%lld] is not finite", who, (long long)(i / C), (long long)(i % C));
+    FSNAP_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    ctx->evd_done = false;
+    if (!ctx->evd_S.ensure((size_t)P * C * 8) || !ctx->evd_beta.ensure((size_t)P * K * 8) || !ctx->evd_info.ensure((size_t)P * 6 * 8) ||
+        !ctx->evd_tab.ensure((size_t)ntab * 8) || !ctx->evd_part.ensure((size_t)npart * 8) ||
+        !ctx->evd_Y.ensure((size_t)PT * C * 16 * 8))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(candidate evidence) failed");
+    std::vector<double> Sm((size_t)P * C);
+    for (size_t i = 0; i < Sm.size(); ++i) Sm[i] = active[i] ? S[i] : 0.0;
+    FSNAP_HIP(hipMemcpyAsync(ctx->evd_S.p, Sm.data(), Sm.size() * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(S)");
+    if (P % 8)                                             // the columns of the last tile that no candidate writes
+        FSNAP_HIP(hipMemsetAsync((double*)ctx->evd_tab.p + (PT - 1) * T * 16, 0, (size_t)T * 16 * 8, ctx->stream), "hipMemsetAsync");
+    for (auto& ev : ctx->evd_ev)
+        if (!ev) FSNAP_HIP(hipEventCreate(&ev), "hipEventCreate");
+    const double* stats = (const double*)ctx->cand_stats.p;
+    const int nblocks = (int)std::min<int64_t>(P, (int64_t)fsnap::cv_blocks_per_cu((int)K) * std::max(1, ctx->num_cu));
+    FSNAP_HIP(hipEventRecord(ctx->evd_ev[0], ctx->stream), "hipEventRecord");
+    FSNAP_HIP(fsnap::launch_evidence_factor(nblocks, stats, (const double*)ctx->evd_S.p, P, C, (int)K, alpha, (double*)ctx->evd_beta.p,
+                                            (double*)ctx->evd_info.p, (double*)ctx->evd_tab.p, ctx->stream),
+              "launch fsnap_evidence_factor_k");
+    FSNAP_HIP(hipEventRecord(ctx->evd_ev[1], ctx->stream), "hipEventRecord");
+    FSNAP_HIP(fsnap::launch_evidence_sweep(stats, (const double*)ctx->evd_tab.p, P, C, (int)K, (double*)ctx->evd_part.p,
+                                           (double*)ctx->evd_Y.p, ctx->stream),
+              "launch fsnap_evidence_sweep_k");
+    FSNAP_HIP(hipEventRecord(ctx->evd_ev[2], ctx->stream), "hipEventRecord");
+    std::vector<double> Y((size_t)PT * C * 16);
+    FSNAP_HIP(hipMemcpyAsync(beta_out, ctx->evd_beta.p, (size_t)P * K * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(beta)");
+    FSNAP_HIP(hipMemcpyAsync(info_out, ctx->evd_info.p, (size_t)P * 6 * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(info)");
+    FSNAP_HIP(hipMemcpyAsync(Y.data(), ctx->evd_Y.p, Y.size() * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(Y)");
+    FSNAP_HIP(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    for (int i = 0; i < 2; ++i) {
+        float ms = 0.0f;
+        FSNAP_HIP(hipEventElapsedTime(&ms, ctx->evd_ev[i], ctx->evd_ev[i + 1]), "hipEventElapsedTime");
+        ctx->evd_ms[i] = ms;
+    }
+    for (int p = 0; p < P; ++p)
+        for (int c = 0; c < C; ++c) {
+            const double* y = Y.data() + (((size_t)(p >> 3) * C + c) * 16 + 2 * (p & 7));
+            terms_out[((int64_t)p * C + c) * 2] = y[0];
+            terms_out[((int64_t)p * C + c) * 2 + 1] = y[1];
+        }
+    ctx->evd_done = true;
+    return FSNAP_OK;                                        // a failed candidate is its own status 1, not the call's
+}
+
+int fsnap_candidates_evidence_times(fsnap_ctx* ctx, double* ms_out) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_candidates_evidence_times";
+    if (!ms_out) return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
+    if (!ctx->evd_done) return ctx->fail(FSNAP_E_STATE, "%s: no fsnap_candidates_evidence call to read from", who);
+    for (int i = 0; i < 2; ++i) ms_out[i] = ctx->evd_ms[i];
     return FSNAP_OK;
 }
 

@@ -167,6 +167,12 @@ struct fsnap_ctx {
     hipEvent_t cvg_ev[4] = {};   // around kernels V0 + G1 (RHS), G2 and G1 (bilinear) of the last call
     double cvg_ms[3] = {};       // their times in ms (fsnap_cv_candidates_grad_times)
     int64_t cvg_g_len = 0;       // doubles of g the last fsnap_cv_candidates_grad left (0: none), for fsnap_cv_candidates_grad_rhs
+    // fsnap_candidates_evidence: masked scales, beta[P][K], info[P][6], the tile tables [ceil(P / 8)][K^2 + K + 3][16], the slice
+    // partials and Y[ceil(P / 8)][C][16]; kept between calls
+    DevBuf evd_S, evd_beta, evd_info, evd_tab, evd_part, evd_Y;
+    hipEvent_t evd_ev[3] = {};   // around kernel E1 and kernels E2 + E3 of the last call
+    double evd_ms[2] = {};       // their times in ms (fsnap_candidates_evidence_times)
+    bool evd_done = false;       // a successful fsnap_candidates_evidence call left its times
     // fsnap_joint_*: the session's unit-sorted row index, unit offsets and per-position weights (uploaded once by begin), the
     // padded factor [M | M B] and B, Z / Pi per position (npos x Wp), the bucketed list of live units, per-unit (gain, reduction)
     // and info, per-workgroup scratch (S and the right-hand-side fragments of units too large for LDS); the host keeps the

@@ -361,6 +361,22 @@ hipError_t launch_cvgrad_solve(int nblocks, const double* rest, const double* to
 hipError_t launch_cvgrad_bilinear(const double* rest, const double* betaT, const double* lamT, int P, int F, int C, int K, double* D,
                                   hipStream_t st);
 
+// Marginal likelihood of weight candidates (fsnap_evidence.hip, K <= CV_MAX_K) on the C packed blocks stats[c] of fsnap_cat_normal_eq.
+// S[P][C]: the scales, 0 for the categories that take no part.  Candidates come in tiles of 8 = 16 table columns:
+// tab[ceil(P / 8)][K^2 + K + 3][16], column 2 (p % 8) = [H^-1 scattered to K x K, zeros at dead columns | 0_K | 0, 0, 0], column
+// 2 (p % 8) + 1 = [beta beta' | -2 beta | 1, 0, 0]; the columns of a last tile without a candidate must be zeroed by the caller.
+// Kernel E1: kernel V1's Jacobi-scaled Cholesky solve of H = sum_c S[p][c]^2 stats[c].G + alpha I on the live columns (dead:
+//            the combined diagonal is 0), log|H|, the in-place inverse; beta[P][K], info[P][6] = (status, smallest scaled pivot,
+//            live columns, log|H|, tr(H^-1), 0), the table columns.  nblocks workgroups of 256 threads stride over the candidates.
+// Kernels E2 + E3: Y[pt][c][16] = sum_e stats[c][e] tab[pt][e][.], the elements in slices of EV_SLICE (partials in
+//            part[ceil(C / 16) ceil(P / 8) evidence_slices(K)][256]), the slices added in index order.  All pointers: device.
+constexpr int EV_SLICE = 512;
+int evidence_slices(int K);
+hipError_t launch_evidence_factor(int nblocks, const double* stats, const double* S, int P, int C, int K, double alpha, double* beta,
+                                  double* info, double* tab, hipStream_t st);
+hipError_t launch_evidence_sweep(const double* stats, const double* tab, int P, int C, int K, double* part, double* Y,
+                                 hipStream_t st);
+
 // Joint unit scores (fsnap_joint.hip).  Kernel J1: for the npos positions of the unit-sorted row index idx,
 // ZP[p] = om[p] a_idx[p] [M | M B] (Wp doubles per position; Fp: device, Kp x Wp row-major, zero-padded: columns [0, Jp) the
 // factor M, columns [Jp, Wp) the target block M B; Wp = Jp without a target; om: the weight of every position).

@@ -287,6 +287,38 @@ class CandidateFits:
 
         return candidates_cv_grad.descend_weights(self, S0, weights, metric, steps, folds, by, seed, eta0, c1, max_halvings)
 
+    def evidence(self, S, alpha=None, scale="profiled", method="auto"):
+        """The marginal likelihood (type-II likelihood, evidence) of the candidates S (P x ncat) and its exact gradient over all
+        category scales (solvers/candidates_evidence.py), the weights w0 S[p, category] read as inverse noise standard
+        deviations.  ``alpha=None`` takes [RIDGE] alpha for RIDGE and 0 for SVD; with alpha > 0 it is MacKay's evidence under
+        the prior beta ~ N(0, 1 / alpha), with alpha = 0 the restricted likelihood of a variance-components model with one
+        component per category.  ``scale="fixed"``: unit noise scale; ``"profiled"``: a common noise scale sigma^2 maximised
+        out.  Returns a ``CandidateEvidence``: ``log_evidence``, ``beta``, ``logdet``, ``sigma2``, ``rss``, ``dof``, ``noise``
+        (= rss / (n - dof) per category), ``grad_logS``, ``grad_logalpha``, ``live``, ``status``, ``min_pivot``.  No folds and
+        no pass over the rows: everything comes from the per-category statistics ``fit`` uses.
+
+        The solve is a plain Jacobi-scaled Cholesky of the normal equations on the live columns (``cross_validate``'s, not
+        ``fit``'s chain); a candidate with a scaled pivot not above 1e-10 has status 1 and NaN in every field, no other
+        candidate changes.  ``method="device"``: ``fsnap_candidates_evidence`` (kernels E1-E3 of csrc/fsnap_evidence.hip,
+        K <= 144, else ValueError); ``"host"``: numpy on the downloaded blocks; ``"auto"``: the device up to 144 columns, the
+        host beyond.  Collective in a multi-rank job (the statistics are already summed over the ranks): every rank returns
+        the same bits.  The layout and its statistics are not touched."""
+        from . import candidates_evidence
+
+        return candidates_evidence.evidence(self, S, alpha, scale, method)
+
+    def maximise_evidence(self, S0, alpha=None, scale="profiled", steps=50, tol=1e-6, damping=1.0, method="auto"):
+        """Batched fixed-point ascent of the evidence on theta = log|S| from the P starts S0 (P x ncat) at once: per iteration
+        one ``evidence`` call, then trial calls for the safeguard.  The step is theta_c += eta / 2 log((n_c - gamma_c) /
+        (kappa lambda_c Q_c)) on the active categories whose numerator and denominator are positive; candidate p accepts it
+        only if its L does not decrease, otherwise eta_p is halved, at most 8 times; after an accepted step eta_p doubles up to
+        ``damping``.  S = 0 stays 0, signs are kept, a NaN candidate is left alone.  A candidate stops when
+        max_c |dL/dlog S[p, c]| / n_c <= ``tol``.  Returns (S (P, ncat), the ``CandidateEvidence`` there, the accepted L per
+        iteration (iterations + 1, P), converged (P,) bool).  alpha is NOT stepped: it stays what the call was given."""
+        from . import candidates_evidence
+
+        return candidates_evidence.maximise_evidence(self, S0, alpha, scale, steps, tol, damping, method)
+
     # ------------------------------------------------------------------------------
     def fit(self, S):
         """(P, K) coefficients of the candidates S (P x ncat); ``info`` gets one dict per candidate: rank, rcond,

@@ -862,6 +862,32 @@ int fsnap_cv_candidates_grad_rhs(fsnap_ctx* ctx, int64_t n, double* g_out);
  * kernels V0 + G1 (RHS epilogue), kernel G2, kernel G1 (bilinear epilogue), in milliseconds.  FSNAP_E_STATE without such a call. */
 int fsnap_cv_candidates_grad_times(fsnap_ctx* ctx, double* ms_out);
 
+/* Marginal likelihood (evidence) of weight candidates from the per-category statistics of `layout` (kernels E1, E2, E3 of
+ * csrc/fsnap_evidence.hip; the definitions, the float64 assembly of L and its gradients, and the ascent are
+ * solvers/candidates_evidence.py).  S (host, P x ncat, row-major, finite) scales category c of candidate p; active (host,
+ * P x ncat, uint8) is 0 where the category takes no part (a testing category, S = 0, no row of non-zero base weight): its scale
+ * counts as 0.  Per candidate, with lambda_c = S[p][c]^2 over the active categories (c ascending, one fma per term):
+ *     H = sum_c lambda_c G_c + alpha I,  D = sqrt(diag H),  beta = D^-1 (D^-1 H D^-1)^-1 D^-1 sum_c lambda_c r_c   (live columns)
+ * by fsnap_cv_candidates' Jacobi-scaled Cholesky; column j is dead (beta_j = 0, left out) when sum_c lambda_c G_c,jj == 0; a pivot
+ * of the scaled matrix that is not > 1e-10 ends the candidate with status 1; the call still returns FSNAP_OK.  Outputs (host):
+ *     beta_out[P][K]        beta (NaN with status 1)
+ *     info_out[P][6]        status (0 / 1), the smallest scaled pivot met (inf without a live column), live columns,
+ *                           log|H| = 2 sum_j (log l_jj + log d_j) (j ascending), tr(H^-1), 0          (NaN with status 1)
+ *     terms_out[P][ncat][2] T_c = tr(H^-1 G_c) and Q_c = bb_c - 2 beta . r_c + beta' G_c beta         (0 with status 1)
+ * The terms are one fp64 MFMA product of the blocks with two table columns per candidate, [H^-1 | 0 | 0,0,0] and
+ * [beta beta' | -2 beta | 1,0,0], the K^2 + K + 3 elements in slices of 512 added in index order: a block is read once per 8
+ * candidates.  FSNAP_E_ARG: K outside 1 ... 144 or not the order of the statistics, ncat not the layout's, P < 1, a non-finite S,
+ * a negative or non-finite alpha, a NULL pointer, or P candidates whose packed buffers, tables (16 ceil(P / 8) (K^2 + K + 3)
+ * doubles) or slice partials pass FSNAP_CAT_STATS_MAX_BYTES.  FSNAP_E_STATE: the context no longer holds the layout or its
+ * statistics.  fp64, no atomics; every sum runs in an order fixed by K and ncat alone: a candidate's bits do not depend on the
+ * batch, the grid or the run.  Nothing resident is touched.  Synchronous. */
+int fsnap_candidates_evidence(fsnap_ctx* ctx, int64_t layout, double alpha, const double* S, int P, int ncat, int64_t K,
+                              const uint8_t* active, double* beta_out, double* info_out, double* terms_out);
+
+/* Device times of the last successful fsnap_candidates_evidence call on this context, from events on its stream: ms_out[2] =
+ * kernel E1, kernels E2 + E3, in milliseconds.  FSNAP_E_STATE without such a call. */
+int fsnap_candidates_evidence_times(fsnap_ctx* ctx, double* ms_out);
+
 /* ---- multi-GPU: one process per GPU; RCCL or one-shot peer-to-peer over xGMI -------- */
 
 /* The reference's data-parallel form of this path (examples/library/transpose_trick/example.py:230-254): every MPI
