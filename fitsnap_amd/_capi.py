@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from collections import namedtuple
 from ctypes import POINTER, byref, c_char_p, c_double, c_int, c_int64, c_uint8, c_void_p
 
 import numpy as np
@@ -37,6 +38,10 @@ ROBUST_HUBER, ROBUST_BISQUARE, ROBUST_CAUCHY = 0, 1, 2   # fsnap_robust_reweight
 ROBUST_LOSSES = {"huber": ROBUST_HUBER, "bisquare": ROBUST_BISQUARE, "cauchy": ROBUST_CAUCHY}
 OMP_OMP, OMP_OLS = 0, 1                         # fsnap_omp_gram / fsnap_omp_path: criterion
 OMP_CRITERIA = {"omp": OMP_OMP, "ols": OMP_OLS}
+BCS_REFERENCE, BCS_EXACT = 0, 1                 # fsnap_bcs_gram / fsnap_bcs_path: deletion
+BCS_DELETIONS = {"reference": BCS_REFERENCE, "exact": BCS_EXACT}
+BCS_RE, BCS_ADD, BCS_DEL, BCS_STOP = 0, 1, 2, 3  # the action of a pick
+BCS_MAX_K, BCS_MAX_ACTIVE = 144, 64             # fsnap_bcs_path (the host route takes any)
 ROBUST_MAX_CLASSES = 32
 MERR_METHODS = {"iid": MERR_IID, "abc": MERR_ABC, "full": MERR_FULL}
 
@@ -81,6 +86,9 @@ SIGNATURES = {
                                  POINTER(c_int64), POINTER(c_double)]),
     "fsnap_omp_gram": (c_int, [c_int64, c_void_p, c_void_p, c_double, c_void_p, c_int, c_void_p, c_int64, c_int64, c_void_p,
                                c_void_p, c_void_p]),
+    "fsnap_bcs_gram": (c_int, [c_int64, c_void_p, c_void_p, c_double, c_double, c_double, c_void_p, c_double, c_double, c_double,
+                               c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p]),
     "fsnap_normal_eq_accumulate": (c_int, [c_void_p, c_void_p]),
     "fsnap_assemble_accumulate": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int,
@@ -154,6 +162,8 @@ SIGNATURES = {
                                c_void_p, c_void_p, c_void_p]),
     "fsnap_omp_path": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int64, c_int64, c_void_p,
                                c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fsnap_bcs_path": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fsnap_select_begin": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int]),
     "fsnap_select_pick": (c_int, [c_void_p, c_int, POINTER(ctypes.c_int32), POINTER(c_double)]),
     "fsnap_select_retire": (c_int, [c_void_p, ctypes.c_int32]),
@@ -345,6 +355,55 @@ def omp_gram(Q: np.ndarray, q: np.ndarray, y2: float, steps: int, criterion="ols
                             _ptr(forced) if forced.size else None, forced.size, S, _ptr(order), _ptr(path), _ptr(coef))
     raise_status(rc, "" if rc != E_ARG else f"fsnap_omp_gram: bad argument (K = {K}, steps = {S}, forced = {forced.tolist()})")
     return order, path, coef
+
+
+def bcs_deletion(deletion) -> int:
+    """The code of "reference" / "exact" (or of a code already); ValueError for anything else."""
+    if isinstance(deletion, str) and deletion.lower() in BCS_DELETIONS:
+        return BCS_DELETIONS[deletion.lower()]
+    if not isinstance(deletion, (str, bool)) and deletion in (BCS_REFERENCE, BCS_EXACT):
+        return int(deletion)
+    raise ValueError(f"deletion must be one of {', '.join(BCS_DELETIONS)}, not {deletion!r}")
+
+
+BcsFit = namedtuple("BcsFit", ["coef", "active", "alpha", "mu", "errbars", "Sig", "picks", "iterations", "status", "sigma2_in",
+                               "sigma2", "rss", "margin"])
+
+
+def bcs_gram(Q: np.ndarray, q: np.ndarray, y2: float, sum_y: float, n: float, sigma2=None, scale=0.01, eta=1e-18, itermax=10,
+             max_active=0, deletion="reference", diag_ref=None):
+    """BCS on the statistics (fsnap_bcs_gram; host side, no GPU needed): the reference's ``bcs()`` recurrence on Q = A^T A,
+    q = A^T y, y2 = |y|^2, sum_y = sum y and n rows.  ``sigma2`` None: max(scale var(y), 1e-16); ``max_active`` 0: K;
+    ``deletion`` "reference" (what the reference computes) or "exact" (Tipping & Faul's deletion); ``diag_ref``: the diagonal
+    the dead-column rule compares Q's with (None: Q's own).  Returns a ``BcsFit``: coef (K), active (the columns in order),
+    alpha, mu, errbars (by position), Sig (n_active x n_active, unclipped), picks (itermax x 2 int32: column, action 0
+    re-estimate / 1 add / 2 delete / 3 chosen but stopped; -1 after the end), iterations, status (0 ended by a stop rule, 1
+    failed -- NaN coefficients --, 2 itermax reached), sigma2_in, sigma2 (re-estimated), rss, margin."""
+    lib = load_library()
+    Q = _f64(Q, "Q")
+    q = _f64(q, "q")
+    K = q.shape[0]
+    if Q.shape != (K, K):
+        raise ValueError("Q must be K x K")
+    ref = None if diag_ref is None else _f64(diag_ref, "diag_ref")
+    if ref is not None and ref.shape != (K,):
+        raise ValueError("diag_ref must have K entries")
+    MA = int(max_active) if int(max_active) != 0 else K
+    P = int(itermax)
+    a = max(MA, 0)
+    coef = np.empty(K)
+    active = np.empty(a, dtype=np.int32)
+    alpha, mu, err, Sig = np.empty(a), np.empty(a), np.empty(a), np.empty((a, a))
+    picks = np.empty((max(P, 0), 2), dtype=np.int32)
+    info = np.empty(6)
+    rc = lib.fsnap_bcs_gram(K, _ptr(Q), _ptr(q), float(y2), float(sum_y), float(n), _ptr(ref),
+                            0.0 if sigma2 is None else float(sigma2), float(scale), float(eta), P, MA, bcs_deletion(deletion),
+                            _ptr(coef), _ptr(active), _ptr(alpha), _ptr(mu), _ptr(err), _ptr(Sig), _ptr(picks), _ptr(info))
+    raise_status(rc, "" if rc != E_ARG else f"fsnap_bcs_gram: bad argument (K = {K}, sigma2 = {sigma2}, scale = {scale}, "
+                                            f"eta = {eta}, itermax = {P}, max_active = {MA})")
+    na = int(np.count_nonzero(active >= 0))
+    return BcsFit(coef, active[:na].copy(), alpha[:na].copy(), mu[:na].copy(), err[:na].copy(), Sig[:na, :na].copy(), picks,
+                  int(info[0]), int(info[1]), float(info[2]), float(info[3]), float(info[4]), float(info[5]))
 
 
 def rowspace_chain(factors, z, rcond, active=None):
@@ -1305,6 +1364,34 @@ class HipContext:
                                              _ptr(forced) if forced.size else None, forced.size, S, _ptr(levels) if Q else None, Q,
                                              _ptr(order), _ptr(path), _ptr(held), _ptr(coef)))
         return order, path, held, coef
+
+    def bcs_path(self, d_stats_ptr: int, K: int, F: int, nsub: int, hyper, max_active: int, deletion="reference"):
+        """Grouped K-fold BCS sparsity path on per-fold statistics in device memory (``fsnap_bcs_path``, K <= 144, max_active
+        <= min(K, 64)): ``d_stats_ptr`` as for ``lasso_path``; ``hyper`` (Q x 4: sigma2 or 0, scale, eta, itermax of every
+        setting; sigma2 = 0: scale x the variance of the problem's own rows).  With P = the largest itermax, returns (coef
+        ((F + 1) x Q x K; index F: no fold left out), active ((F + 1) x Q x max_active int32, -1 past the active set), alpha
+        and errbars (the same shape, by position), picks ((F + 1) x Q x P x 2 int32), info ((F + 1) x Q x 6: iterations,
+        status, sigma2 used, sigma2 re-estimated, rss, margin), heldout (F x Q x 3: n_f, weighted squared error of fold f
+        under its own refit, bb_f), Sig (Q x max_active x max_active of the fits on all rows))."""
+        hyper = _f64(hyper, "hyper")
+        K, F, MA = int(K), int(F), int(max_active)
+        if hyper.ndim != 2 or hyper.shape[1] != 4:
+            raise ValueError(f"hyper must have shape (Q, 4), not {hyper.shape}")
+        Q = hyper.shape[0]
+        its = hyper[:, 3] if Q else np.zeros(0)
+        P = int(its.max()) if Q and np.all(np.isfinite(its)) and its.max() >= 1 and its.max() <= 65536 else 1
+        n1, a = max(F, 0) + 1, max(MA, 0)
+        coef = np.empty((n1, Q, max(K, 0)))
+        active = np.empty((n1, Q, a), dtype=np.int32)
+        alpha, err = np.empty((n1, Q, a)), np.empty((n1, Q, a))
+        picks = np.empty((n1, Q, P, 2), dtype=np.int32)
+        info = np.empty((n1, Q, 6))
+        held = np.empty((max(F, 0), Q, 3))
+        Sig = np.empty((Q, a, a))
+        self._check(self._lib.fsnap_bcs_path(self._h, K, F, int(nsub), c_void_p(d_stats_ptr), _ptr(hyper) if Q else None, Q, MA,
+                                             bcs_deletion(deletion), _ptr(coef), _ptr(active), _ptr(alpha), _ptr(err),
+                                             _ptr(picks), _ptr(info), _ptr(held), _ptr(Sig)))
+        return coef, active, alpha, err, picks, info, held, Sig
 
     def ard_path(self, d_stats_ptr: int, K: int, F: int, nsub: int, hyper, max_iter: int, tol: float):
         """Grouped K-fold ARD threshold path on per-fold statistics in device memory (``fsnap_ard_path``, K <= 144):

@@ -17,6 +17,8 @@ defaulted here, with the reference's defaults:
                                                             (solvers/robust.py; no counterpart in the reference)
   [OMP]    terms, criterion=ols, forced= (comma-separated column indices)
                                                             (solvers/omp.py; no counterpart in the reference)
+  [BCS]    sigma2= (blank: scale x var(bw)), scale=0.01, eta=1.0E-18, itermax=10, max_active=0 (min(K, 64)),
+           deletion=reference                                (solvers/bcs.py; the reference's bcs() hard-codes them)
   [EXTRAS] apply_transpose, multinode_testing, only_test, dump_*   (extras.py:19-45)
   [CALCULATOR] calculator, energy, force, stress, per_atom_energy, linear
                                                             (calculator_sections/calculator.py:17-32)
@@ -29,6 +31,7 @@ A section that belongs to an un-selected solver raises UserWarning like the refe
 from __future__ import annotations
 
 import configparser
+import math
 from types import SimpleNamespace
 
 _BOOL_TRUE = {"1", "true", "yes", "on"}
@@ -230,6 +233,36 @@ class Config:
             if terms < 0:
                 raise RuntimeError(f">>> [OMP] terms = {terms}: at least 1 (or 0 for every column)")
             self.sections["OMP"] = SimpleNamespace(name="OMP", terms=terms, criterion=criterion, forced=tuple(forced))
+
+        if "BCS" in raw or solver.upper() == "BCS":
+            bd = raw.get("BCS", {})
+            _check_keys("BCS", bd, ["sigma2", "scale", "eta", "itermax", "max_active", "deletion"])
+            if solver.upper() != "BCS":
+                not_used("BCS")
+            s2 = str(_get(bd, "sigma2", "", "str")).strip()
+            try:
+                sigma2 = float(s2) if s2 else None
+            except ValueError:
+                raise RuntimeError(f">>> [BCS] sigma2 = {s2}: a positive number, or blank for scale x var(bw)")
+            scale = _get(bd, "scale", "0.01", "float")
+            eta = _get(bd, "eta", "1.0E-18", "float")
+            itermax = _get(bd, "itermax", "10", "int")
+            max_active = _get(bd, "max_active", "0", "int")
+            deletion = _get(bd, "deletion", "reference", "str").strip().lower()
+            if sigma2 is not None and not (math.isfinite(sigma2) and sigma2 > 0.0):
+                raise RuntimeError(f">>> [BCS] sigma2 = {sigma2}: a positive number, or blank for scale x var(bw)")
+            if not (math.isfinite(scale) and scale > 0.0):
+                raise RuntimeError(f">>> [BCS] scale = {scale}: a positive number")
+            if not (math.isfinite(eta) and eta >= 0.0):
+                raise RuntimeError(f">>> [BCS] eta = {eta}: not negative")
+            if itermax < 1:
+                raise RuntimeError(f">>> [BCS] itermax = {itermax}: at least 1")
+            if max_active < 0:
+                raise RuntimeError(f">>> [BCS] max_active = {max_active}: at least 1 (or 0 for min(K, 64))")
+            if deletion not in ("reference", "exact"):
+                raise RuntimeError(f">>> [BCS] deletion = {deletion}: one of reference, exact")
+            self.sections["BCS"] = SimpleNamespace(name="BCS", sigma2=sigma2, scale=scale, eta=eta, itermax=itermax,
+                                                   max_active=max_active, deletion=deletion)
 
         if "ROBUST" in raw or solver.upper() == "ROBUST":
             rb = raw.get("ROBUST", {})

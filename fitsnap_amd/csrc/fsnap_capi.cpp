@@ -3274,6 +3274,62 @@ int fsnap_omp_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const dou
                        coef_out, nprob * Q * K);
 }
 
+// ---- grouped K-fold BCS sparsity paths on the per-fold statistics (kernel S1 of fsnap_lasso.hip, B1 of fsnap_bcs.hip) ------
+
+int fsnap_bcs_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const double* d_stats, const double* hyper, int64_t Q,
+                   int64_t max_active, int deletion, double* coef_out, int32_t* active_out, double* alpha_out,
+                   double* errbar_out, int32_t* picks_out, double* info_out, double* heldout_out, double* sig_out) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_bcs_path";
+    if (!hyper || !coef_out || !active_out || !alpha_out || !errbar_out || !picks_out || !info_out || !heldout_out || !sig_out)
+        return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
+    int rc = fold_check(ctx, who, K, fsnap::BCS_MAX_K, F, nsub, Q, Q, d_stats);
+    if (rc) return rc;
+    if (max_active < 1 || max_active > K || max_active > fsnap::BCS_MAX_ACTIVE)
+        return ctx->fail(FSNAP_E_ARG, "%s: max_active = %lld (1 ... min(K, %d))", who, (long long)max_active, fsnap::BCS_MAX_ACTIVE);
+    if (deletion != FSNAP_BCS_REFERENCE && deletion != FSNAP_BCS_EXACT) return ctx->fail(FSNAP_E_ARG, "%s: deletion = %d", who, deletion);
+    int64_t P = 1;
+    for (int64_t i = 0; i < Q; ++i) {
+        const double *h = hyper + i * 4, it = h[3];
+        const bool ok = std::isfinite(h[0]) && std::isfinite(h[1]) && std::isfinite(h[2]) && std::isfinite(it) && h[0] >= 0.0 &&
+                        (h[0] > 0.0 || h[1] > 0.0) && h[2] >= 0.0 && it >= 1.0 && it <= 65536.0 && it == std::floor(it);
+        if (!ok)
+            return ctx->fail(FSNAP_E_ARG, "%s: hyper[%lld] = (%g, %g, %g, %g)", who, (long long)i, h[0], h[1], h[2], h[3]);
+        P = std::max<int64_t>(P, (int64_t)it);
+    }
+    const int64_t nprob = (F + 1) * Q, MA = max_active;
+    if ((double)nprob * (double)P * 8.0 > (double)FSNAP_CAT_STATS_MAX_BYTES)
+        return ctx->fail(FSNAP_E_ARG, "%s: %lld problems x %lld picks", who, (long long)nprob, (long long)P);
+    const double *dfolds, *dtotal;
+    if ((rc = fold_stage(ctx, who, K, F, nsub, d_stats, &dfolds, &dtotal))) return rc;
+    if (!ctx->bcs_hyper.ensure((size_t)Q * 4 * 8) || !ctx->bcs_coef.ensure((size_t)nprob * K * 8) ||
+        !ctx->bcs_int.ensure((size_t)nprob * (MA + 2 * P) * 4) || !ctx->bcs_pos.ensure((size_t)nprob * MA * 2 * 8) ||
+        !ctx->bcs_info.ensure((size_t)nprob * 6 * 8) || !ctx->bcs_held.ensure((size_t)F * Q * 3 * 8) ||
+        !ctx->bcs_sig.ensure((size_t)Q * MA * MA * 8))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(bcs path) failed");
+    int* dactive = (int*)ctx->bcs_int.p;
+    int* dpicks = dactive + nprob * MA;
+    double* dalpha = (double*)ctx->bcs_pos.p;
+    double* derr = dalpha + nprob * MA;
+    FSNAP_HIP(hipMemcpyAsync(ctx->bcs_hyper.p, hyper, (size_t)Q * 4 * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(hyper)");
+    FSNAP_HIP(fsnap::launch_bcs_path(fold_grid(ctx, nprob, fsnap::bcs_blocks_per_cu((int)K, (int)MA)), dfolds, dtotal,
+                                     (const double*)ctx->bcs_hyper.p, (int)K, (int)F, (int)Q, (int)MA, (int)P,
+                                     deletion == FSNAP_BCS_EXACT ? 1 : 0, (double*)ctx->bcs_coef.p, dactive, dalpha, derr, dpicks,
+                                     (double*)ctx->bcs_info.p, (double*)ctx->bcs_held.p, (double*)ctx->bcs_sig.p, ctx->stream),
+              "launch fsnap_bcs_path_k");
+    // no scan: a failed problem is its own status 1, not the call's
+    return fold_finish(ctx,
+                       {{coef_out, ctx->bcs_coef.p, (size_t)nprob * K * 8},
+                        {active_out, dactive, (size_t)nprob * MA * 4},
+                        {picks_out, dpicks, (size_t)nprob * P * 2 * 4},
+                        {alpha_out, dalpha, (size_t)nprob * MA * 8},
+                        {errbar_out, derr, (size_t)nprob * MA * 8},
+                        {info_out, ctx->bcs_info.p, (size_t)nprob * 6 * 8},
+                        {heldout_out, ctx->bcs_held.p, (size_t)F * Q * 3 * 8},
+                        {sig_out, ctx->bcs_sig.p, (size_t)Q * MA * MA * 8}},
+                       nullptr, 0);
+}
+
 // ---- grouped K-fold cross-validation of weight candidates (kernels V0, V1, V2 of fsnap_cv.hip) -----------------------------
 
 int fsnap_cv_candidates(fsnap_ctx* ctx, int64_t layout, double alpha, const double* S, int P, int F, int C, int64_t K,

@@ -158,6 +158,8 @@ struct fsnap_ctx {
     DevBuf ard_hyper, ard_coef, ard_lambda, ard_info, ard_held;
     // fsnap_omp_path: [forced | levels], orders, path rows, held-out sums, coefficients; kept between calls
     DevBuf omp_in, omp_order, omp_path, omp_held, omp_coef;
+    // fsnap_bcs_path: hyper, coefficients, [active | picks], [alpha | errbars], info, held-out sums, Sig; kept between calls
+    DevBuf bcs_hyper, bcs_coef, bcs_int, bcs_pos, bcs_info, bcs_held, bcs_sig;
     // fsnap_cv_candidates / fsnap_cv_candidate_rows: per-category totals followed by the F C blocks total - fold, scales, coefficients, info, the per-fold coefficient
     // tables of a launch (the chunk partials and sums share cand_rpart / cand_res); kept between calls
     DevBuf cv_total, cv_S, cv_coef, cv_info, cv_betaT;

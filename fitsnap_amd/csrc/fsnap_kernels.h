@@ -326,6 +326,22 @@ hipError_t launch_omp_path(int nblocks, const double* folds, const double* total
                            int nforced, int S, const int* levels, int Q, int* order, double* path, double* heldout, double* coef,
                            hipStream_t st);
 
+// Grouped K-fold BCS sparsity paths (fsnap_bcs.hip; K <= BCS_MAX_K, max_active <= min(K, BCS_MAX_ACTIVE)) on the folds and the
+// total of kernel S1.  Kernel B1: problem p = f Q + q (f = F: no fold left out) is fsnap_bcs_gram's recurrence on (total -
+// folds[f]) with diag_ref = the total's diagonal and hyper[q][4] = (sigma2 or 0, scale, eta, itermax); sigma2 = 0 takes scale x
+// the variance of the problem's own rows.  coef[p][K], active[p][max_active] (-1 past the active set), alpha and
+// errbars[p][max_active] by position, picks[p][P][2] (P >= every itermax), info[p][6] = (iterations, status 0 ended / 1 failed /
+// 2 itermax reached, sigma2 used, sigma2 re-estimated, rss, margin), heldout[p][3] (p < F Q) = (n_f, bb_f - 2 beta . c_f +
+// beta^T G_f beta, bb_f), sig[q][max_active][max_active] of the f = F problems.  exact: 0 = the reference's deletion, 1 = Tipping
+// & Faul's.  One workgroup of 256 threads per problem, nblocks workgroups stride over the problems.  All pointers: device.
+constexpr int BCS_MAX_K = 144;
+constexpr int BCS_MAX_ACTIVE = 64;
+size_t bcs_lds_bytes(int K, int max_active);
+int bcs_blocks_per_cu(int K, int max_active);
+hipError_t launch_bcs_path(int nblocks, const double* folds, const double* total, const double* hyper, int K, int F, int Q,
+                           int max_active, int P, int exact, double* coef, int* active, double* alpha, double* errbars, int* picks,
+                           double* info, double* heldout, double* sig, hipStream_t st);
+
 // Grouped K-fold cross-validation of weight candidates (fsnap_cv.hip; V1: K <= CV_MAX_K) on the F * C packed blocks of
 // fsnap_cat_normal_eq with composite category f * C + c.  Kernel V0: total[c] = sum_f stats[f * C + c], folds in index order,
 // and rest[f * C + c] = total[c] - stats[f * C + c] (F C blocks).

@@ -1560,3 +1560,247 @@ extern "C" int fsnap_omp_gram(int64_t K64, const double* Q, const double* q, dou
     }
     return all_finite(coef, (size_t)S * n) ? FSNAP_OK : FSNAP_NUM_NONFINITE;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// BCS on the statistics: the fast relevance-vector recurrence (Tipping & Faul 2003, as coded by Ji for Bayesian compressive
+// sensing; fitsnap3lib/solvers/bcs.py, bcs()) restated on (Q = A^T A, q = A^T y, y2, sum y, n).  The statements, their order and
+// the nugget are the reference's; what it forms from rows is formed from Q (include/fsnap_hip.h lists every departure).  The
+// per-column formulas are fsnap_bcs_body.h's, shared with kernel B1 (fsnap_bcs.hip), which runs this text with the columns
+// spread over a workgroup.  Sums over the active set run with the position ascending, one fma per term.
+// ---------------------------------------------------------------------------------------------------------------------
+#include "fsnap_bcs_body.h"
+
+extern "C" int fsnap_bcs_gram(int64_t K64, const double* Q, const double* q, double y2, double sum_y, double n,
+                              const double* diag_ref, double sigma2, double scale, double eta, int64_t itermax64,
+                              int64_t max_active64, int deletion, double* coef, int32_t* active, double* alpha_out, double* mu_out,
+                              double* errbars, double* Sig_out, int32_t* picks, double* info) {
+    using namespace fsnap;
+    if (!Q || !q || !coef || !active || !alpha_out || !mu_out || !errbars || !Sig_out || !picks || !info) return FSNAP_E_ARG;
+    if (K64 < 1 || K64 > (1 << 20) || itermax64 < 1 || itermax64 > (1 << 24) || max_active64 < 1 || max_active64 > K64)
+        return FSNAP_E_ARG;
+    if (deletion != FSNAP_BCS_REFERENCE && deletion != FSNAP_BCS_EXACT) return FSNAP_E_ARG;
+    if (!(std::isfinite(eta) && eta >= 0.0)) return FSNAP_E_ARG;
+    if (!(std::isfinite(sigma2) && sigma2 >= 0.0)) return FSNAP_E_ARG;
+    if (sigma2 == 0.0 && !(std::isfinite(scale) && scale > 0.0)) return FSNAP_E_ARG;
+    const int K = (int)K64, MA = (int)max_active64, itermax = (int)itermax64;
+    if (!all_finite(Q, (size_t)K * K) || !all_finite(q, K) || !std::isfinite(y2) || !std::isfinite(sum_y) || !std::isfinite(n))
+        return FSNAP_NUM_NONFINITE;
+    if (diag_ref && !all_finite(diag_ref, K)) return FSNAP_NUM_NONFINITE;
+    const double nug = BCS_NUGGET, tol = 1e-10, inf = std::numeric_limits<double>::infinity();
+    const double s2 = sigma2 > 0.0 ? sigma2 : bcs_sigma2(scale, y2, sum_y, n);
+    const bool exact = deletion == FSNAP_BCS_EXACT;
+
+    vec S((size_t)K, 0.0), Qv((size_t)K, 0.0), ml((size_t)K), th((size_t)K), ssv((size_t)K);
+    vec al((size_t)MA, 0.0), mu((size_t)MA, 0.0), Sg((size_t)MA * MA, 0.0), sigi((size_t)MA), c1((size_t)MA);
+    std::vector<int> pos((size_t)K, -1), idx((size_t)MA, -1);
+    std::vector<unsigned char> dead((size_t)K);
+    for (int i = 0; i < 2 * itermax; ++i) picks[i] = -1;
+    for (int j = 0; j < K; ++j) coef[j] = 0.0;
+
+    int i0 = -1, na = 0, iters = 0, status = 0;
+    double br = 0.0, margin = inf;
+    for (int j = 0; j < K; ++j) {
+        const double qjj = Q[(size_t)j * K + j], ref = diag_ref ? diag_ref[j] : qjj;
+        dead[j] = ref == 0.0 || qjj <= tol * ref;
+        if (dead[j]) continue;
+        const double r = bcs_ratio(q[j], qjj);
+        if (i0 < 0 || r > br) {
+            i0 = j;
+            br = r;
+        }
+    }
+    if (i0 >= 0) {
+        const double Qii = Q[(size_t)i0 * K + i0], qi = q[i0];
+        const double alpha0 = Qii / (br - s2);
+        const double Sg00 = 1.0 / ((alpha0 + Qii / s2) + nug);
+        Sg[0] = Sg00;
+        mu[0] = Sg00 * qi / s2;
+        al[0] = alpha0;
+        idx[0] = i0;
+        pos[i0] = 0;
+        na = 1;
+        for (int j = 0; j < K; ++j) {
+            if (dead[j]) continue;
+            const double left = Q[(size_t)i0 * K + j] / s2;
+            S[j] = Q[(size_t)j * K + j] / s2 - Sg00 * (left * left);
+            Qv[j] = q[j] / s2 - ((Sg00 * qi) / s2) * left;
+        }
+        double ml0 = 0.0, mlprev = 0.0;
+        status = 2;
+        for (int count = 0; count < itermax; ++count) {
+            int ib = -1, i2 = -1;
+            for (int j = 0; j < K; ++j) {
+                ml[j] = -inf;
+                if (dead[j]) continue;
+                const BcsScore sc = bcs_score(S[j], Qv[j], pos[j] >= 0, pos[j] >= 0 ? al[pos[j]] : 0.0, na < MA);
+                ml[j] = sc.ml;
+                th[j] = sc.theta;
+                ssv[j] = sc.ss;
+                if (sc.ml != -inf && (ib < 0 || bcs_before(sc.ml, j, ml[ib], ib))) ib = j;
+            }
+            if (ib < 0) {                                   // a guard: an active column always scores, so only a formula that
+                                                            // returns -inf gets here (the reference would idle to itermax)
+                status = 0;
+                break;
+            }
+            for (int j = 0; j < K; ++j)
+                if (j != ib && ml[j] != -inf && (i2 < 0 || bcs_before(ml[j], j, ml[i2], i2))) i2 = j;
+            const double mlb = ml[ib];
+            if (i2 >= 0) {
+                const double m = (mlb - ml[i2]) / std::fabs(mlb);
+                if (m < margin) margin = m;
+            }
+            iters = count + 1;
+            if (count == 0) ml0 = mlb;
+            const bool stop = count > 1 && std::fabs(mlb - mlprev) < std::fabs(mlb - ml0) * eta;
+            mlprev = mlb;
+            picks[2 * count] = ib;
+            if (stop) {
+                picks[2 * count + 1] = BCS_STOP;
+                status = 0;
+                break;
+            }
+            const int pb = pos[ib];
+            if (th[ib] > 0.0) {
+                const double a_new = ssv[ib] * ssv[ib] / th[ib] + nug;
+                if (pb >= 0) {                              // re-estimate
+                    const double Sigii = Sg[(size_t)pb * MA + pb], mui = mu[pb];
+                    for (int a = 0; a < na; ++a) sigi[a] = Sg[(size_t)a * MA + pb];
+                    const double delta = a_new - al[pb];
+                    const double ki = delta / (1.0 + Sigii * delta);
+                    for (int a = 0; a < na; ++a) mu[a] -= (ki * mui) * sigi[a];
+                    for (int a = 0; a < na; ++a)
+                        for (int b = 0; b < na; ++b) Sg[(size_t)a * MA + b] -= ki * (sigi[a] * sigi[b]);
+                    for (int j = 0; j < K; ++j) {
+                        if (dead[j]) continue;
+                        double c = 0.0;
+                        for (int a = 0; a < na; ++a) c = std::fma(Q[(size_t)idx[a] * K + j], sigi[a], c);
+                        c /= s2;
+                        S[j] += ki * (c * c);
+                        Qv[j] += (ki * mui) * c;
+                    }
+                    al[pb] = a_new;
+                    picks[2 * count + 1] = BCS_RE;
+                } else {                                    // add
+                    const double Sigii = 1.0 / (a_new + S[ib]);
+                    const double mui = Sigii * Qv[ib];
+                    const double* Qi = Q + (size_t)ib * K;
+                    for (int a = 0; a < na; ++a) {
+                        double t = 0.0;
+                        for (int b = 0; b < na; ++b) t = std::fma(Sg[(size_t)a * MA + b], Q[(size_t)idx[b] * K + ib], t);
+                        c1[a] = t / s2;
+                    }
+                    for (int j = 0; j < K; ++j) {
+                        if (dead[j]) continue;
+                        double c = 0.0;
+                        for (int a = 0; a < na; ++a) c = std::fma(Q[(size_t)idx[a] * K + j], c1[a], c);
+                        const double c2 = (Qi[j] - c) / s2;
+                        S[j] -= Sigii * (c2 * c2);
+                        Qv[j] -= mui * c2;
+                    }
+                    for (int a = 0; a < na; ++a)
+                        for (int b = 0; b < na; ++b) Sg[(size_t)a * MA + b] += Sigii * (c1[a] * c1[b]);
+                    for (int a = 0; a < na; ++a) {
+                        const double off = -Sigii * c1[a];
+                        Sg[(size_t)a * MA + na] = off;
+                        Sg[(size_t)na * MA + a] = off;
+                        mu[a] -= mui * c1[a];
+                    }
+                    Sg[(size_t)na * MA + na] = Sigii;
+                    mu[na] = mui;
+                    al[na] = a_new;
+                    idx[na] = ib;
+                    pos[ib] = na;
+                    ++na;
+                    picks[2 * count + 1] = BCS_ADD;
+                }
+            } else if (pb < 0) {                            // an inactive column without theta > 0 (its ml is NaN): the reference
+                picks[2 * count + 1] = BCS_STOP;            // idles on this state until itermax
+                status = 0;
+                break;
+            } else {                                        // delete
+                if (na > 1) {
+                    const double Sigii = Sg[(size_t)pb * MA + pb], mui = mu[pb];
+                    for (int a = 0; a < na; ++a) sigi[a] = Sg[(size_t)a * MA + pb];
+                    for (int a = 0; a < na; ++a)
+                        for (int b = 0; b < na; ++b) Sg[(size_t)a * MA + b] -= (sigi[a] * sigi[b]) / Sigii;
+                    if (exact) {
+                        // the reference reads Sig[:, p] through a view that its own in-place downdate has just zeroed, so
+                        // there these three updates change nothing
+                        for (int a = 0; a < na; ++a) mu[a] -= (mui / Sigii) * sigi[a];
+                        for (int j = 0; j < K; ++j) {
+                            if (dead[j]) continue;
+                            double c = 0.0;
+                            for (int a = 0; a < na; ++a) c = std::fma(Q[(size_t)idx[a] * K + j], sigi[a], c);
+                            c /= s2;
+                            S[j] += (c * c) / Sigii;
+                            Qv[j] += (mui / Sigii) * c;
+                        }
+                    }
+                    for (int a = 0, ao = 0; ao < na; ++ao) {    // compact: row and column pb leave
+                        if (ao == pb) continue;
+                        for (int b = 0, bo = 0; bo < na; ++bo) {
+                            if (bo == pb) continue;
+                            Sg[(size_t)a * MA + b] = Sg[(size_t)ao * MA + bo];
+                            ++b;
+                        }
+                        mu[a] = mu[ao];
+                        al[a] = al[ao];
+                        idx[a] = idx[ao];
+                        pos[idx[a]] = a;
+                        ++a;
+                    }
+                    pos[ib] = -1;
+                    --na;
+                    picks[2 * count + 1] = BCS_DEL;
+                } else {
+                    picks[2 * count + 1] = BCS_STOP;
+                }
+                if (na == 1) {
+                    status = 0;
+                    break;
+                }
+            }
+        }
+    }
+    // the fit, the re-estimated noise variance and the check the reference asserts
+    double mq = 0.0, mQm = 0.0, ad = 0.0;
+    for (int a = 0; a < na; ++a) {
+        double t = 0.0;
+        for (int b = 0; b < na; ++b) t = std::fma(Q[(size_t)idx[a] * K + idx[b]], mu[b], t);
+        mq = std::fma(mu[a], q[idx[a]], mq);
+        mQm = std::fma(mu[a], t, mQm);
+        ad = std::fma(al[a], Sg[(size_t)a * MA + a], ad);
+    }
+    const double rss = std::fma(-2.0, mq, y2) + mQm;
+    const double s2_new = rss / (n - (double)na + ad);
+    bool ok = true;
+    for (int a = 0; a < MA; ++a) {
+        active[a] = a < na ? idx[a] : -1;
+        alpha_out[a] = a < na ? al[a] : 0.0;
+        mu_out[a] = a < na ? mu[a] : 0.0;
+        const double d = a < na ? Sg[(size_t)a * MA + a] : 0.0;
+        errbars[a] = std::sqrt(d < 0.0 ? 0.0 : d);
+        ok = ok && std::isfinite(mu_out[a]) && std::isfinite(errbars[a]);
+        for (int b = 0; b < MA; ++b) Sig_out[(size_t)a * MA + b] = (a < na && b < na) ? Sg[(size_t)a * MA + b] : 0.0;
+    }
+    // det(Sig) > -nugget by symmetric elimination without pivoting (on the work copy, which is not needed any more)
+    double det = 1.0;
+    for (int k = 0; k < na; ++k) {
+        const double piv = Sg[(size_t)k * MA + k];
+        det *= piv;
+        for (int a = k + 1; a < na; ++a)
+            for (int b = k + 1; b < na; ++b) Sg[(size_t)a * MA + b] -= Sg[(size_t)a * MA + k] * Sg[(size_t)k * MA + b] / piv;
+    }
+    if (!ok || !(det > -nug)) status = 1;
+    for (int a = 0; a < na; ++a) coef[idx[a]] = mu[a];
+    if (status == 1)
+        for (int j = 0; j < K; ++j) coef[j] = std::numeric_limits<double>::quiet_NaN();
+    info[0] = (double)iters;
+    info[1] = (double)status;
+    info[2] = s2;
+    info[3] = s2_new;
+    info[4] = rss;
+    info[5] = margin;
+    return FSNAP_OK;                                        // a failed problem is its own status 1, not the call's
+}

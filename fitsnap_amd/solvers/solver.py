@@ -25,7 +25,7 @@ import numpy as np
 
 from .. import _capi
 from .._hostblas import blas_threads
-from . import ard_path, influence, lasso_path, loco, loco_uq, omp_path, ridge_path, select, select_joint, uq
+from . import ard_path, bcs_path, influence, lasso_path, loco, loco_uq, omp_path, ridge_path, select, select_joint, uq
 
 
 class _TrainWeights:
@@ -1275,6 +1275,35 @@ class Solver:
         ``cv_se`` of it.  Neither the fit nor the config is changed.  Raises ValueError for other solvers, for
         ``apply_transpose``, for an empty grid and for unknown grid keys."""
         return ard_path.ard_path(self, grid, folds, by, fs_dict, b, w, tol, max_iter, method, table, seed)
+
+    # ------------------------------------------------------------------------------
+    # grouped K-fold BCS sparsity paths (solvers/bcs_path.py, csrc/fsnap_bcs.hip)
+    # ------------------------------------------------------------------------------
+    def bcs_path(self, grid, folds=5, by="Configs", fs_dict=None, b=None, w=None, method="auto", table="auto", seed=0):
+        """Grouped K-fold cross-validation of the BCS fit over a grid of ``[BCS]`` settings, after ``perform_fit`` of a BCS
+        solver, from ONE pass over the resident training rows: the units (``fs_dict[by]``, as in ``loco_errors``) are dealt
+        into folds as in ``lasso_path``, the statistics of every fold are formed on the GPU and every (fold left out, setting)
+        refit plus the fit on all rows per setting runs the BCS recurrence (``fsnap_bcs_gram``) on "total minus fold".
+        ``grid``: a sequence of mappings that override ``sigma2`` (None: ``scale`` x the variance of the rows that remain),
+        ``scale``, ``eta``, ``itermax``; a sequence of numbers stands for ``scale`` values.  ``max_active`` and ``deletion``
+        are the ``[BCS]`` section's.  ``method``: "device" (the kernel, K <= 144 and max_active <= 64), "host"
+        (``fsnap_bcs_gram`` over the downloaded fold statistics, any K) or "auto" (the kernel where it exists; the routes
+        agree closely, not to the bit: the device's ``log`` is not the host's).  ``folds``, ``table``, labels, truths and
+        weights as in ``lasso_path``; the table is keyed (setting, Row_Type) by the position in the grid.  Collective on
+        several ranks; a unit may span ranks.
+
+        Returns ``bcs_path.BcsPath``: ``grid`` (the complete settings), ``fits`` (Q x K, on all training rows), ``nonzeros``,
+        ``active`` (Q x max_active, the support in order, -1 past it), ``errbars`` (by position), ``covs`` (Q x K x K, as
+        ``perform_fit`` forms ``cov``), ``sigma2`` ((F + 1) x Q, re-estimated), ``iterations``, ``status`` (0 ended by a stop
+        rule, 1 failed, 2 itermax reached), ``margin`` (the smallest relative gap between the best and the second-best
+        marginal likelihood of an iteration), ``picks`` ((F + 1) x Q x P x 2: column and action per iteration), ``table``,
+        ``fold_of_unit``, ``cv_error`` / ``cv_se`` (pooled weighted held-out mean squared error per setting and its
+        standard error over the folds; NaN for a setting with a failed refit), ``best`` / ``best_setting`` (the smallest
+        ``cv_error``, ties to fewer non-zeros) and ``sparsest`` / ``sparsest_setting`` (the fewest non-zeros within one
+        ``cv_se`` of it), ``frequency`` (per column, the share of the refits that kept it at the best setting).  Neither the
+        fit nor the config is changed.  Raises ValueError for other solvers, for ``apply_transpose``, for an empty grid and
+        for unknown grid keys."""
+        return bcs_path.bcs_path(self, grid, folds, by, fs_dict, b, w, method, table, seed)
 
     # ------------------------------------------------------------------------------
     # grouped K-fold greedy sparse-selection paths (solvers/omp_path.py, csrc/fsnap_omp.hip)

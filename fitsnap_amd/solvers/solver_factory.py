@@ -3,7 +3,7 @@ direct subclass of ``Solver`` whose class name equals ``[SOLVER] solver`` case-i
 IndexError.  The imports below are the registration."""
 from .._discovery import find_plugin
 from .solver import Solver
-from . import anl, ard, lasso, mcmc, merr, omp, ridge, robust, svd  # noqa: F401  (ANL, ARD, LASSO, MCMC, MERR, OMP, RIDGE, ROBUST, SVD)
+from . import anl, ard, bcs, lasso, mcmc, merr, omp, ridge, robust, svd  # noqa: F401  (ANL, ARD, BCS, LASSO, MCMC, MERR, OMP, RIDGE, ROBUST, SVD)
 
 
 def search(solver_name):

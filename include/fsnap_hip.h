@@ -500,6 +500,30 @@ int fsnap_omp_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const dou
                    const int32_t* forced, int64_t nforced, int64_t S, const int32_t* levels, int64_t Q, int32_t* order_out,
                    double* path_out, double* heldout_out, double* coef_out);
 
+/* Grouped K-fold BCS sparsity paths on per-fold statistics (kernel S1 of csrc/fsnap_lasso.hip, B1 of csrc/fsnap_bcs.hip; the
+ * grid, the host route, the picks and the tables are solvers/bcs_path.py).  d_stats (DEVICE), the folds and the total T as for
+ * fsnap_lasso_path.  Problem (f, q), f < F: the refit of setting q without fold f; f = F: on all training rows:
+ *     Qm = T.G - G_f,  qv = T.c - c_f,  y2 = T.bb - bb_f,  sum_y = T.sum wb - sum wb_f,  n = T.n - n_f     (f = F: T alone)
+ * run through fsnap_bcs_gram's recurrence (below) with diag_ref = T.G_jj, max_active and deletion, and with
+ * hyper[q] = (sigma2 or 0, scale, eta, itermax) (host, Q x 4): a setting with sigma2 = 0 takes sigma2 = max(scale (y2 / n -
+ * (sum_y / n)^2), 1e-16) from the problem's OWN downdated scalars.  P = the largest itermax of the settings.  Outputs (host):
+ * coef_out[(F + 1)][Q][K]; active_out[(F + 1)][Q][max_active] (int32, the active columns in order, then -1), alpha_out and
+ * errbar_out[(F + 1)][Q][max_active] by position (0 past the active set); picks_out[(F + 1)][Q][P][2] (int32: column, action;
+ * -1 after the end); info_out[(F + 1)][Q][6] as fsnap_bcs_gram's; heldout_out[F][Q][3] = n_f, bb_f - 2 beta . c_f + beta^T G_f
+ * beta (the weighted squared error of fold f under its own refit), bb_f; sig_out[Q][max_active][max_active] = Sig of the f = F
+ * problems (unclipped, zero past the active set).  A problem that fails has status 1 and NaN coefficients; the call still
+ * returns FSNAP_OK.  FSNAP_E_ARG for K outside 1 ... 144, max_active outside 1 ... min(K, 64), F < 1, nsub < 1, Q < 1, an
+ * unknown deletion, a NULL pointer, a hyper row with sigma2 < 0, sigma2 = 0 and scale <= 0, eta < 0, an itermax outside
+ * 1 ... 65 536 or not an integer, or any entry not finite, or F * nsub blocks past FSNAP_CAT_STATS_MAX_BYTES.  One workgroup of
+ * 256 threads per problem (thread j owns column j); fp64 VALU, no atomics; every sum runs in an order that depends on the
+ * problem alone and the argmax compares (ml, index) exactly with the lowest index on equality: bit-identical run to run and
+ * under any permutation or subset of the grid or the folds.  The device's log differs from the host's in the last bits, so
+ * the results are close to fsnap_bcs_gram's, not identical.  The resident rows, weights, mask and category layout are not
+ * touched.  Synchronous. */
+int fsnap_bcs_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const double* d_stats, const double* hyper, int64_t Q,
+                   int64_t max_active, int deletion, double* coef_out, int32_t* active_out, double* alpha_out,
+                   double* errbar_out, int32_t* picks_out, double* info_out, double* heldout_out, double* sig_out);
+
 /* Joint scores of units (normally configurations) of the resident rows for active learning (kernels J1, J2 of
  * csrc/fsnap_joint.hip, fp64 MFMA; the host algebra is solvers/select_joint.py).  With the posterior C = M M^T (M: K x J),
  * the noise variance tau of a unit-weight row, the weighted rows X_u = diag(omega) A_u (n_u x K) of unit u, Z = X_u M and a
@@ -624,6 +648,41 @@ int fsnap_lasso_gram(int64_t K, const double* Q, const double* q, double y_norm2
  * FSNAP_NUM_NONFINITE for a NaN/Inf in the statistics.  Host side, no context needed. */
 int fsnap_omp_gram(int64_t K, const double* Q, const double* q, double y2, const double* diag_ref, int criterion,
                    const int32_t* forced, int64_t nforced, int64_t S, int32_t* order, double* path, double* coef);
+
+/* BCS on the statistics: Bayesian compressive sensing by the fast relevance-vector recurrence of Tipping & Faul, the reference's
+ * bcs() (fitsnap3lib/solvers/bcs.py) with Q = A^T A (K x K, row-major, symmetric), q = A^T y, y2 = |y|^2, sum_y = sum y and n
+ * rows.  sigma2 > 0: the initial noise variance; sigma2 = 0: max(scale (y2 / n - (sum_y / n)^2), 1e-16) (the reference's rule is
+ * scale = 0.01).  State: the active columns in order with alpha, mu and Sig by position, S_j and Q_j per column.  Kept from the
+ * reference statement for statement: the 1e-16 nugget in its five places; the initial column argmax (q_j^2 + nugget) / (Q_jj
+ * + nugget); per iteration ss, qq (rescaled for active columns), theta = qq^2 - ss and the three ml formulas (re-estimate and
+ * add for theta > 0, delete for an active column with theta <= 0); argmax ml in numpy's order (a NaN wins; the lowest index on equality); the stop test
+ * after the pick, for the third and later iterations only, |ml_t - ml_{t-1}| < |ml_t - ml_0| eta; the re-estimate, add and
+ * delete updates (append at the end, compact on deletion); the end when a deletion is asked for and one column is left (before
+ * or after it); sigma2_new = rss / (n - n_active + sum alpha_p Sig_pp) with rss = y2 - 2 mu . q_s + mu^T Q_ss mu.
+ * deletion = FSNAP_BCS_REFERENCE computes what the reference computes: its deletion reads Sig[:, p] through a view that its
+ * own in-place downdate of Sig has zeroed, so mu only loses its entry and S, Q stay stale; FSNAP_BCS_EXACT applies Tipping &
+ * Faul's updates of mu, S and Q.  Departures: (1) what the reference forms from rows is formed from Q: comm_j = (sum_a Q[s_a, j]
+ * Sig_ap) / sigma2 and comm2_j = (Q[i, j] - sum_a Q[s_a, j] comm1_a) / sigma2, sums with the position a ascending, one fma per
+ * term; (2) column j is dead -- never a candidate, not for the initial pick either, coefficient 0 -- when diag_ref[j] == 0 or
+ * Q_jj <= 1e-10 diag_ref[j] (diag_ref = NULL: Q's own diagonal); (3) with max_active columns active, inactive columns are not
+ * candidates; (4) an iteration without a candidate, or whose pick is an inactive column without theta > 0, ends the problem
+ * (the reference would repeat a no-op to itermax); the argmax keeps numpy's order: a NaN ml wins, as it does in the reference
+ * after a deletion has left S stale; (5) the reference's assert det(Sig) > -nugget is status 1 (the determinant by
+ * symmetric elimination without pivoting), as is a non-finite mu or errbar: such a problem has NaN coefficients and the call
+ * still returns FSNAP_OK; (6) itermax is an argument (the reference hard-codes 10).
+ * Outputs: coef[K] (mu on the active columns, 0 elsewhere); active[max_active] (int32, in order, then -1); alpha, mu,
+ * errbars[max_active] by position (errbars = sqrt(max(Sig_pp, 0)), 0 past the active set); Sig[max_active][max_active]
+ * (unclipped, zero past the active set); picks[itermax][2] (int32: column and action 0 re-estimate / 1 add / 2 delete / 3 chosen
+ * but stopped; -1 after the end); info[6] = iterations that chose a column, status (0 ended by a stop rule, 1 failed, 2
+ * itermax reached), sigma2 as used, sigma2_new, rss, margin = the smallest (ml_best - ml_second) / |ml_best| over the
+ * iterations (inf when there never was a second candidate).  FSNAP_E_ARG for K < 1, itermax < 1, max_active outside 1 ... K,
+ * an unknown deletion, sigma2 < 0, sigma2 = 0 with scale <= 0, eta < 0, any of them not finite, or a NULL pointer (diag_ref
+ * may be NULL); FSNAP_NUM_NONFINITE for a NaN/Inf in the statistics.  Host side, no context needed. */
+#define FSNAP_BCS_REFERENCE 0
+#define FSNAP_BCS_EXACT 1
+int fsnap_bcs_gram(int64_t K, const double* Q, const double* q, double y2, double sum_y, double n, const double* diag_ref,
+                   double sigma2, double scale, double eta, int64_t itermax, int64_t max_active, int deletion, double* coef,
+                   int32_t* active, double* alpha, double* mu, double* errbars, double* Sig, int32_t* picks, double* info);
 
 /* Same solve, taking the packed statistics [G | c | ...] from DEVICE memory (the buffer
  * fsnap_normal_eq_async / the all-reduce left in HBM).  Small systems are copied to the host
