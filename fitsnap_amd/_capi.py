@@ -42,6 +42,7 @@ BCS_REFERENCE, BCS_EXACT = 0, 1                 # fsnap_bcs_gram / fsnap_bcs_pat
 BCS_DELETIONS = {"reference": BCS_REFERENCE, "exact": BCS_EXACT}
 BCS_RE, BCS_ADD, BCS_DEL, BCS_STOP = 0, 1, 2, 3  # the action of a pick
 BCS_MAX_K, BCS_MAX_ACTIVE = 144, 64             # fsnap_bcs_path (the host route takes any)
+SPEC_MAX_K = 144                                # fsnap_spectral_path (the host route takes any)
 ROBUST_MAX_CLASSES = 32
 MERR_METHODS = {"iid": MERR_IID, "abc": MERR_ABC, "full": MERR_FULL}
 
@@ -89,6 +90,8 @@ SIGNATURES = {
     "fsnap_bcs_gram": (c_int, [c_int64, c_void_p, c_void_p, c_double, c_double, c_double, c_void_p, c_double, c_double, c_double,
                                c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p]),
+    "fsnap_spectral_gram": (c_int, [c_int64, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "fsnap_normal_eq_accumulate": (c_int, [c_void_p, c_void_p]),
     "fsnap_assemble_accumulate": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int,
@@ -164,6 +167,9 @@ SIGNATURES = {
                                c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fsnap_bcs_path": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fsnap_spectral_path": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fsnap_spectral_path_times": (c_int, [c_void_p, c_void_p]),
     "fsnap_select_begin": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int]),
     "fsnap_select_pick": (c_int, [c_void_p, c_int, POINTER(ctypes.c_int32), POINTER(c_double)]),
     "fsnap_select_retire": (c_int, [c_void_p, ctypes.c_int32]),
@@ -404,6 +410,40 @@ def bcs_gram(Q: np.ndarray, q: np.ndarray, y2: float, sum_y: float, n: float, si
     na = int(np.count_nonzero(active >= 0))
     return BcsFit(coef, active[:na].copy(), alpha[:na].copy(), mu[:na].copy(), err[:na].copy(), Sig[:na, :na].copy(), picks,
                   int(info[0]), int(info[1]), float(info[2]), float(info[3]), float(info[4]), float(info[5]))
+
+
+SpectralFit = namedtuple("SpectralFit", ["eig", "z", "n_live", "sweeps", "off_ratio", "lambda_max", "lambda_min", "status", "rank",
+                                         "dof", "sse", "coef"])
+
+
+def spectral_gram(Q: np.ndarray, q: np.ndarray, y2: float, alphas, rconds, diag_ref=None):
+    """Spectral path of one system on the statistics (fsnap_spectral_gram; host side, no GPU needed): one Jacobi
+    eigendecomposition of the live block of Q = A^T A, then the fit of every setting (alpha, rcond) of the product grid, q =
+    ia * len(rconds) + ir: g_i = z_i / (lambda_i + alpha) on the directions with lambda_i > max(rcond^2, 4 n_live eps)
+    lambda_max.  ``diag_ref``: the diagonal the dead-column rule compares Q's with (None: Q's own).  Returns a
+    ``SpectralFit``: eig and z (K, ascending, zero past n_live), n_live, sweeps, off_ratio, lambda_max, lambda_min, status (0
+    converged, 2 sweep cap), rank, dof, sse (each Qa x Qr) and coef (Qa x Qr x K)."""
+    lib = load_library()
+    Q = _f64(Q, "Q")
+    q = _f64(q, "q")
+    K = q.shape[0]
+    if Q.shape != (K, K):
+        raise ValueError("Q must be K x K")
+    ref = None if diag_ref is None else _f64(diag_ref, "diag_ref")
+    if ref is not None and ref.shape != (K,):
+        raise ValueError("diag_ref must have K entries")
+    alphas = _f64(alphas, "alphas").reshape(-1)
+    rconds = _f64(rconds, "rconds").reshape(-1)
+    Qa, Qr = alphas.size, rconds.size
+    eig, z, info = np.empty(K), np.empty(K), np.empty(6)
+    sets = np.empty((Qa, Qr, 3))
+    coef = np.empty((Qa, Qr, K))
+    rc = lib.fsnap_spectral_gram(K, _ptr(Q), _ptr(q), float(y2), _ptr(ref), _ptr(alphas) if Qa else None, Qa,
+                                 _ptr(rconds) if Qr else None, Qr, _ptr(eig), _ptr(z), _ptr(info), _ptr(sets), _ptr(coef))
+    raise_status(rc, "" if rc != E_ARG else f"fsnap_spectral_gram: bad argument (K = {K}, alphas = {alphas.tolist()}, "
+                                            f"rconds = {rconds.tolist()})")
+    return SpectralFit(eig, z, int(info[0]), int(info[1]), float(info[2]), float(info[3]), float(info[4]), int(info[5]),
+                       sets[:, :, 0].astype(np.int64), sets[:, :, 1].copy(), sets[:, :, 2].copy(), coef)
 
 
 def rowspace_chain(factors, z, rcond, active=None):
@@ -1392,6 +1432,33 @@ class HipContext:
                                              bcs_deletion(deletion), _ptr(coef), _ptr(active), _ptr(alpha), _ptr(err),
                                              _ptr(picks), _ptr(info), _ptr(held), _ptr(Sig)))
         return coef, active, alpha, err, picks, info, held, Sig
+
+    def spectral_path(self, d_stats_ptr: int, K: int, F: int, nsub: int, alphas, rconds, want_coef: bool = True):
+        """Grouped K-fold spectral path on per-fold statistics in device memory (``fsnap_spectral_path``, K <= 144):
+        ``d_stats_ptr`` as for ``lasso_path``; the settings are the product grid of ``alphas`` and ``rconds``, q = ia * Qr + ir.
+        Returns (eig and z ((F + 1) x K, ascending, zero past n_live; index F: no fold left out), info ((F + 1) x 6: n_live,
+        sweeps, final off / diag ratio, lambda_max, smallest lambda, status 0 converged / 2 sweep cap), sets ((F + 1) x Q x 3:
+        rank, dof, sse), fits (Q x K, on all rows), coef (F x Q x K of the refits, or None without ``want_coef``), heldout (F
+        x Q x nsub x 3: n, weighted squared error of class s of fold f under the fold's own refit, bb))."""
+        alphas = _f64(alphas, "alphas").reshape(-1)
+        rconds = _f64(rconds, "rconds").reshape(-1)
+        K, F, nsub, Qa, Qr = int(K), int(F), int(nsub), alphas.size, rconds.size
+        Q, n1, k = Qa * Qr, max(F, 0) + 1, max(K, 0)
+        eig, z, info = np.empty((n1, k)), np.empty((n1, k)), np.empty((n1, 6))
+        sets = np.empty((n1, Q, 3))
+        fits = np.empty((Q, k))
+        coef = np.empty((max(F, 0), Q, k)) if want_coef else None
+        held = np.empty((max(F, 0), Q, max(nsub, 0), 3))
+        self._check(self._lib.fsnap_spectral_path(self._h, K, F, nsub, c_void_p(d_stats_ptr), _ptr(alphas) if Qa else None, Qa,
+                                                  _ptr(rconds) if Qr else None, Qr, _ptr(eig), _ptr(z), _ptr(info), _ptr(sets),
+                                                  _ptr(fits), _ptr(coef), _ptr(held)))
+        return eig, z, info, sets, fits, coef, held
+
+    def spectral_path_times(self):
+        """(ms of kernel E1, ms of kernel E2) of the last ``spectral_path`` call (``fsnap_spectral_path_times``)."""
+        ms = np.zeros(2)
+        self._check(self._lib.fsnap_spectral_path_times(self._h, _ptr(ms)))
+        return float(ms[0]), float(ms[1])
 
     def ard_path(self, d_stats_ptr: int, K: int, F: int, nsub: int, hyper, max_iter: int, tol: float):
         """Grouped K-fold ARD threshold path on per-fold statistics in device memory (``fsnap_ard_path``, K <= 144):

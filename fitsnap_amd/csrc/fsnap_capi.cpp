@@ -857,6 +857,8 @@ int fsnap_ctx_destroy(fsnap_ctx* ctx) {
         if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : ctx->evd_ev)
         if (ev) (void)hipEventDestroy(ev);
+    for (auto& ev : ctx->spec_ev)
+        if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : ctx->ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto& sl : ctx->ring)
@@ -3328,6 +3330,99 @@ int fsnap_bcs_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const dou
                         {heldout_out, ctx->bcs_held.p, (size_t)F * Q * 3 * 8},
                         {sig_out, ctx->bcs_sig.p, (size_t)Q * MA * MA * 8}},
                        nullptr, 0);
+}
+
+// ---- grouped K-fold spectral paths on the per-fold statistics (kernel S1 of fsnap_lasso.hip, E1 / E2 of fsnap_spectral.hip) --
+
+int fsnap_spectral_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const double* d_stats, const double* alphas,
+                        int64_t Qa, const double* rconds, int64_t Qr, double* eig_out, double* z_out, double* info_out,
+                        double* set_out, double* fit_out, double* coef_out, double* heldout_out) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_spectral_path";
+    if (!alphas || !rconds || !eig_out || !z_out || !info_out || !set_out || !fit_out || !heldout_out)
+        return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
+    if (Qa < 1 || Qr < 1 || Qa > 0xFFFFF || Qr > 0xFFFFF)
+        return ctx->fail(FSNAP_E_ARG, "%s: Qa = %lld, Qr = %lld", who, (long long)Qa, (long long)Qr);
+    const int64_t Q = Qa * Qr;
+    int rc = fold_check(ctx, who, K, fsnap::SPEC_MAX_K, F, nsub, Q, Q, d_stats);
+    if (rc) return rc;
+    for (int64_t i = 0; i < Qa; ++i)
+        if (!std::isfinite(alphas[i]) || alphas[i] < 0.0)
+            return ctx->fail(FSNAP_E_ARG, "%s: alphas[%lld] = %g is negative or not finite", who, (long long)i, alphas[i]);
+    for (int64_t i = 0; i < Qr; ++i)
+        if (!std::isfinite(rconds[i]) || rconds[i] < 0.0)
+            return ctx->fail(FSNAP_E_ARG, "%s: rconds[%lld] = %g is negative or not finite", who, (long long)i, rconds[i]);
+    const int64_t nprob = F + 1;
+    const double cap = (double)FSNAP_CAT_STATS_MAX_BYTES;
+    if ((double)F * (double)Q * (double)nsub * 24.0 > cap || (coef_out && (double)nprob * (double)Q * (double)K * 8.0 > cap))
+        return ctx->fail(FSNAP_E_ARG, "%s: %lld folds x %lld settings of results exceed FSNAP_CAT_STATS_MAX_BYTES", who,
+                         (long long)F, (long long)Q);
+    if (!cand_fits(F * nsub, K))                                      // fold_stage's own refusal, taken before anything is forgotten
+        return ctx->fail(FSNAP_E_ARG, "%s: %lld blocks x %lld doubles exceed FSNAP_CAT_STATS_MAX_BYTES", who, (long long)(F * nsub),
+                         (long long)FSNAP_PACKED_LEN(K));
+    ctx->spec_done = false;                                           // from here on kernels are queued: the last call's times go
+    const double *dfolds, *dtotal;
+    if ((rc = fold_stage(ctx, who, K, F, nsub, d_stats, &dfolds, &dtotal))) return rc;
+    const int nb1 = fold_grid(ctx, nprob, fsnap::spectral_eig_blocks_per_cu((int)K));
+    const int nb2 = fold_grid(ctx, nprob * fsnap::spectral_slices((int)Q), fsnap::spectral_eval_blocks_per_cu((int)K));
+    const size_t nwork = fsnap::spectral_vectors_in_lds((int)K) ? 1 : (size_t)nb1 * K * K;
+    const size_t ncoef = (size_t)(coef_out ? nprob : 1) * Q * K;       // [fit | coefficients of the F refits]
+    if (!ctx->spec_grid.ensure((size_t)Q * 2 * 8) || !ctx->spec_eig.ensure((size_t)nprob * K * 8) ||
+        !ctx->spec_z.ensure((size_t)nprob * K * 8) || !ctx->spec_V.ensure((size_t)nprob * K * K * 8) ||
+        !ctx->spec_info.ensure((size_t)nprob * 6 * 8) || !ctx->spec_work.ensure(nwork * 8) ||
+        !ctx->spec_set.ensure((size_t)nprob * Q * 3 * 8) || !ctx->spec_coef.ensure(ncoef * 8) ||
+        !ctx->spec_held.ensure((size_t)F * Q * nsub * 3 * 8))
+        return ctx->fail(FSNAP_E_NOMEM, "hipMalloc(spectral path) failed");
+    std::vector<double> grid((size_t)Q * 2);                          // setting q = ia Qr + ir
+    for (int64_t ia = 0; ia < Qa; ++ia)
+        for (int64_t ir = 0; ir < Qr; ++ir) {
+            grid[(size_t)(ia * Qr + ir)] = alphas[ia];
+            grid[(size_t)(Q + ia * Qr + ir)] = rconds[ir];
+        }
+    for (auto& ev : ctx->spec_ev)
+        if (!ev) FSNAP_HIP(hipEventCreate(&ev), "hipEventCreate");
+    double* dgrid = (double*)ctx->spec_grid.p;
+    double* dfit = (double*)ctx->spec_coef.p;
+    double* dcoef = coef_out ? dfit + Q * K : nullptr;
+    FSNAP_HIP(hipMemcpyAsync(dgrid, grid.data(), grid.size() * 8, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(grid)");
+    FSNAP_HIP(hipEventRecord(ctx->spec_ev[0], ctx->stream), "hipEventRecord");
+    FSNAP_HIP(fsnap::launch_spectral_eig(nb1, dfolds, dtotal, (int)K, (int)F, (double*)ctx->spec_work.p, (double*)ctx->spec_eig.p,
+                                         (double*)ctx->spec_z.p, (double*)ctx->spec_V.p, (double*)ctx->spec_info.p, ctx->stream),
+              "launch fsnap_spectral_eig_k");
+    FSNAP_HIP(hipEventRecord(ctx->spec_ev[1], ctx->stream), "hipEventRecord");
+    FSNAP_HIP(fsnap::launch_spectral_eval(nb2, d_stats, dfolds, dtotal, (const double*)ctx->spec_eig.p, (const double*)ctx->spec_z.p,
+                                          (const double*)ctx->spec_V.p, (const double*)ctx->spec_info.p, dgrid, dgrid + Q, (int)K,
+                                          (int)F, (int)nsub, (int)Q, (double*)ctx->spec_set.p, dfit, dcoef,
+                                          (double*)ctx->spec_held.p, ctx->stream),
+              "launch fsnap_spectral_eval_k");
+    FSNAP_HIP(hipEventRecord(ctx->spec_ev[2], ctx->stream), "hipEventRecord");
+    if (coef_out)
+        FSNAP_HIP(hipMemcpyAsync(coef_out, dcoef, (size_t)F * Q * K * 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy(coef)");
+    rc = fold_finish(ctx,
+                     {{eig_out, ctx->spec_eig.p, (size_t)nprob * K * 8},
+                      {z_out, ctx->spec_z.p, (size_t)nprob * K * 8},
+                      {info_out, ctx->spec_info.p, (size_t)nprob * 6 * 8},
+                      {set_out, ctx->spec_set.p, (size_t)nprob * Q * 3 * 8},
+                      {fit_out, dfit, (size_t)Q * K * 8},
+                      {heldout_out, ctx->spec_held.p, (size_t)F * Q * nsub * 3 * 8}},
+                     fit_out, Q * K);
+    if (rc) return rc;
+    for (int i = 0; i < 2; ++i) {
+        float ms = 0.0f;
+        FSNAP_HIP(hipEventElapsedTime(&ms, ctx->spec_ev[i], ctx->spec_ev[i + 1]), "hipEventElapsedTime");
+        ctx->spec_ms[i] = ms;
+    }
+    ctx->spec_done = true;
+    return FSNAP_OK;
+}
+
+int fsnap_spectral_path_times(fsnap_ctx* ctx, double* ms_out) {
+    if (!ctx) return FSNAP_E_ARG;
+    const char* who = "fsnap_spectral_path_times";
+    if (!ms_out) return ctx->fail(FSNAP_E_ARG, "%s: NULL argument", who);
+    if (!ctx->spec_done) return ctx->fail(FSNAP_E_STATE, "%s: no fsnap_spectral_path call to read from", who);
+    for (int i = 0; i < 2; ++i) ms_out[i] = ctx->spec_ms[i];
+    return FSNAP_OK;
 }
 
 // ---- grouped K-fold cross-validation of weight candidates (kernels V0, V1, V2 of fsnap_cv.hip) -----------------------------

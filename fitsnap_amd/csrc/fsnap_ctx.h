@@ -160,6 +160,12 @@ struct fsnap_ctx {
     DevBuf omp_in, omp_order, omp_path, omp_held, omp_coef;
     // fsnap_bcs_path: hyper, coefficients, [active | picks], [alpha | errbars], info, held-out sums, Sig; kept between calls
     DevBuf bcs_hyper, bcs_coef, bcs_int, bcs_pos, bcs_info, bcs_held, bcs_sig;
+    // fsnap_spectral_path: [alphas | rconds] of the Q settings, eigenvalues, z, eigenvectors, info, the per-workgroup eigenvector
+    // scratch of kernel E1 (fsnap_spectral.hip), rank / dof / sse, [fit | coefficients], held-out sums; kept between calls
+    DevBuf spec_grid, spec_eig, spec_z, spec_V, spec_info, spec_work, spec_set, spec_coef, spec_held;
+    hipEvent_t spec_ev[3] = {};  // around kernel E1 and kernel E2 (fsnap_spectral.hip) of the last call
+    double spec_ms[2] = {};      // their times in ms (fsnap_spectral_path_times)
+    bool spec_done = false;      // a successful fsnap_spectral_path call left its times
     // fsnap_cv_candidates / fsnap_cv_candidate_rows: per-category totals followed by the F C blocks total - fold, scales, coefficients, info, the per-fold coefficient
     // tables of a launch (the chunk partials and sums share cand_rpart / cand_res); kept between calls
     DevBuf cv_total, cv_S, cv_coef, cv_info, cv_betaT;

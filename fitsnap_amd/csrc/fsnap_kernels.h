@@ -342,6 +342,29 @@ hipError_t launch_bcs_path(int nblocks, const double* folds, const double* total
                            int max_active, int P, int exact, double* coef, int* active, double* alpha, double* errbars, int* picks,
                            double* info, double* heldout, double* sig, hipStream_t st);
 
+// Grouped K-fold spectral paths (fsnap_spectral.hip; K <= SPEC_MAX_K) on the folds and the total of kernel S1.  Kernel E1:
+// problem f (f = F: no fold left out) is the Jacobi eigendecomposition of the live block of (total - folds[f]) under the
+// round-robin ordering of fsnap_spectral_body.h: eig[f][K] and z[f][K] ascending (zero past n_live), V[f][K][K] (row r < n_live:
+// eigenvector r in the K original coordinates), info[f][6] = (n_live, sweeps, final off / diag ratio, lambda_max, smallest
+// lambda, status 0 converged / 2 sweep cap).  vwork: nblocks x K^2 doubles of scratch (read and written only where
+// spectral_vectors_in_lds(K) is false).  Kernel E2: work item (f, slice of 16 settings) evaluates the settings (alphas[q],
+// rconds[q]), q < Q: set[f][Q][3] = (rank, dof, sse), fit[Q][K] (f = F), coef[F][Q][K] (may be nullptr), held[F][Q][nsub][3] =
+// (n_{f,s}, bb_{f,s} - 2 beta . c_{f,s} + beta^T G_{f,s} beta, bb_{f,s}) against block f nsub + s of stats.  One workgroup (E1: 1024
+// threads, E2: 256) per problem / work item, nblocks workgroups stride over them.  All pointers: device.
+constexpr int SPEC_MAX_K = 144;
+size_t spectral_eig_lds_bytes(int K);
+bool spectral_vectors_in_lds(int K);
+int spectral_eig_blocks_per_cu(int K);
+size_t spectral_eval_lds_bytes(int K);
+int spectral_eval_blocks_per_cu(int K);
+int spectral_slices(int Q);
+hipError_t launch_spectral_eig(int nblocks, const double* folds, const double* total, int K, int F, double* vwork, double* eig,
+                               double* z, double* V, double* info, hipStream_t st);
+hipError_t launch_spectral_eval(int nblocks, const double* stats, const double* folds, const double* total, const double* eig,
+                                const double* z, const double* V, const double* info, const double* alphas, const double* rconds,
+                                int K, int F, int nsub, int Q, double* set, double* fit, double* coef, double* held,
+                                hipStream_t st);
+
 // Grouped K-fold cross-validation of weight candidates (fsnap_cv.hip; V1: K <= CV_MAX_K) on the F * C packed blocks of
 // fsnap_cat_normal_eq with composite category f * C + c.  Kernel V0: total[c] = sum_f stats[f * C + c], folds in index order,
 // and rest[f * C + c] = total[c] - stats[f * C + c] (F C blocks).

@@ -1804,3 +1804,168 @@ extern "C" int fsnap_bcs_gram(int64_t K64, const double* Q, const double* q, dou
     info[5] = margin;
     return FSNAP_OK;                                        // a failed problem is its own status 1, not the call's
 }
+
+// Spectral paths on the statistics: ONE Jacobi eigendecomposition of the live block of Q, then every (alpha, rcond) setting as
+// a filter on (lambda, z) (include/fsnap_hip.h, fsnap_spectral_gram).  The statements -- the round-robin pair order, the
+// rotation and its skip rule, the 2 x 2 block update on the packed triangle, the order of the stopping sums (as taken by the
+// 1024 lanes of kernel E1) and the filter -- are fsnap_spectral_body.h's, shared with kernels E1 / E2 (fsnap_spectral.hip),
+// which run this text with the pairs of a round spread over a workgroup.
+#include "fsnap_spectral_body.h"
+
+namespace {
+
+// the sum of the SPEC_LANES lane values as kernel E1 takes it: the xor butterfly 1, 2, ..., 32 inside each wave of 64, then the
+// waves in index order
+double spec_lanes_sum(double* v) {
+    double tmp[64];
+    for (int w = 0; w < fsnap::SPEC_LANES / 64; ++w) {
+        double* x = v + 64 * w;
+        for (int o = 1; o < 64; o <<= 1) {
+            for (int i = 0; i < 64; ++i) tmp[i] = x[i] + x[i ^ o];
+            for (int i = 0; i < 64; ++i) x[i] = tmp[i];
+        }
+    }
+    double s = v[0];
+    for (int w = 1; w < fsnap::SPEC_LANES / 64; ++w) s += v[64 * w];
+    return s;
+}
+
+}  // namespace
+
+extern "C" int fsnap_spectral_gram(int64_t K64, const double* Q, const double* q, double y2, const double* diag_ref,
+                                   const double* alphas, int64_t Qa, const double* rconds, int64_t Qr, double* eig_out,
+                                   double* z_out, double* info_out, double* set_out, double* coef_out) {
+    using namespace fsnap;
+    if (!Q || !q || !alphas || !rconds || !eig_out || !z_out || !info_out || !set_out || !coef_out) return FSNAP_E_ARG;
+    if (K64 < 1 || K64 > (1 << 14) || Qa < 1 || Qr < 1 || Qa > 0xFFFFF || Qr > 0xFFFFF || Qa * Qr > 0xFFFFF) return FSNAP_E_ARG;
+    for (int64_t i = 0; i < Qa; ++i)
+        if (!std::isfinite(alphas[i]) || alphas[i] < 0.0) return FSNAP_E_ARG;
+    for (int64_t i = 0; i < Qr; ++i)
+        if (!std::isfinite(rconds[i]) || rconds[i] < 0.0) return FSNAP_E_ARG;
+    const int K = (int)K64;
+    if (!all_finite(Q, (size_t)K * K) || !all_finite(q, K) || !std::isfinite(y2)) return FSNAP_NUM_NONFINITE;
+    if (diag_ref && !all_finite(diag_ref, K)) return FSNAP_NUM_NONFINITE;
+    const double tol = 1e-10;                               // fsnap::LOCO_PIVOT_TOL
+    std::vector<int> live;
+    for (int j = 0; j < K; ++j) {
+        const double qjj = Q[(size_t)j * K + j], ref = diag_ref ? diag_ref[j] : qjj;
+        if (!(ref == 0.0 || qjj <= tol * ref)) live.push_back(j);
+    }
+    const int n = (int)live.size(), m = n + (n & 1), h = m / 2;
+    vec tri((size_t)n * (n + 1) / 2 + 1), V((size_t)n * n + 1, 0.0), cs((size_t)h + 1), sn((size_t)h + 1);
+    std::vector<int> pp((size_t)h + 1), qq((size_t)h + 1);
+    for (int i = 0; i < n; ++i) {
+        for (int j = 0; j <= i; ++j) tri[spec_tri(i, j)] = Q[(size_t)live[i] * K + live[j]];
+        V[(size_t)i * n + i] = 1.0;
+    }
+    int sweeps = 0, status = 0;
+    double off2 = 0.0, diag2 = 0.0;
+    for (;;) {
+        double po[SPEC_LANES] = {}, pd[SPEC_LANES] = {};
+        for (int idx = 0; idx < n * n; ++idx) {
+            const int i = idx / n, j = idx - i * n, t = idx % SPEC_LANES;
+            if (j > i) continue;
+            const double a = tri[spec_tri(i, j)];
+            if (j == i)
+                pd[t] = fma(a, a, pd[t]);
+            else
+                po[t] = fma(a, a, po[t]);
+        }
+        off2 = spec_lanes_sum(po);
+        diag2 = spec_lanes_sum(pd);
+        if (off2 == 0.0 || off2 <= SPEC_STOP * diag2) break;
+        if (sweeps == SPEC_MAX_SWEEPS) {
+            status = 2;
+            break;
+        }
+        for (int r = 0; r < m - 1; ++r) {
+            for (int k = 0; k < h; ++k) {                   // the rotations of the round, from the matrix before it
+                int p, s;
+                spec_pair(m, r, k, p, s);
+                pp[k] = p;
+                qq[k] = s < n ? s : -1;
+                cs[k] = 1.0;
+                sn[k] = 0.0;
+                if (s >= n) continue;
+                const int ipp = spec_tri(p, p), iqq = spec_tri(s, s), ipq = spec_tri(s, p);
+                const double app = tri[ipp], aqq = tri[iqq], apq = tri[ipq];
+                const SpecRot rot = spec_rot(app, aqq, apq);
+                cs[k] = rot.c;
+                sn[k] = rot.s;
+                tri[ipp] = fma(-rot.t, apq, app);
+                tri[iqq] = fma(rot.t, apq, aqq);
+                tri[ipq] = 0.0;
+            }
+            for (int a = 1; a < h; ++a)                     // the blocks below the diagonal of pairs
+                for (int b = 0; b < a; ++b) {
+                    if (sn[a] == 0.0 && sn[b] == 0.0) continue;
+                    const int pa = pp[a], qa = qq[a], pb = pp[b], qb = qq[b];
+                    double b00 = tri[spec_tri(pa, pb)], b01 = qb >= 0 ? tri[spec_tri(pa, qb)] : 0.0;
+                    double b10 = qa >= 0 ? tri[spec_tri(qa, pb)] : 0.0, b11 = (qa >= 0 && qb >= 0) ? tri[spec_tri(qa, qb)] : 0.0;
+                    spec_block(cs[a], sn[a], cs[b], sn[b], b00, b01, b10, b11);
+                    tri[spec_tri(pa, pb)] = b00;
+                    if (qb >= 0) tri[spec_tri(pa, qb)] = b01;
+                    if (qa >= 0) tri[spec_tri(qa, pb)] = b10;
+                    if (qa >= 0 && qb >= 0) tri[spec_tri(qa, qb)] = b11;
+                }
+            for (int k = 0; k < h; ++k) {                   // eigenvectors: the rows of V
+                if (sn[k] == 0.0) continue;
+                double* vp = V.data() + (size_t)pp[k] * n;
+                double* vq = V.data() + (size_t)qq[k] * n;
+                for (int e = 0; e < n; ++e) spec_apply(cs[k], sn[k], vp[e], vq[e]);
+            }
+        }
+        ++sweeps;
+    }
+    // ascending by (lambda, position on the diagonal)
+    std::vector<int> ord((size_t)n);
+    vec lam((size_t)K, 0.0), z((size_t)K, 0.0);
+    double lmax = 0.0, lmin = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const double li = tri[spec_tri(i, i)];
+        int rk = 0;
+        for (int j = 0; j < n; ++j) {
+            const double lj = tri[spec_tri(j, j)];
+            if (lj < li || (lj == li && j < i)) ++rk;
+        }
+        ord[rk] = i;
+        lam[rk] = li;
+        lmax = std::fabs(li) > lmax ? std::fabs(li) : lmax;
+        lmin = (i == 0 || li < lmin) ? li : lmin;
+    }
+    for (int r = 0; r < n; ++r) {
+        const double* v = V.data() + (size_t)ord[r] * n;
+        double acc = 0.0;
+        for (int c = 0; c < n; ++c) acc = fma(v[c], q[live[c]], acc);
+        z[r] = acc;
+    }
+    for (int i = 0; i < K; ++i) {
+        eig_out[i] = lam[i];
+        z_out[i] = z[i];
+    }
+    info_out[0] = (double)n;
+    info_out[1] = (double)sweeps;
+    info_out[2] = diag2 > 0.0 ? std::sqrt(off2 / diag2) : 0.0;
+    info_out[3] = lmax;
+    info_out[4] = lmin;
+    info_out[5] = (double)status;
+    vec g((size_t)n + 1);
+    for (int64_t ia = 0; ia < Qa; ++ia)
+        for (int64_t ir = 0; ir < Qr; ++ir) {
+            const int64_t s = ia * Qr + ir;
+            const double alpha = alphas[ia], cut = spec_cut(rconds[ir], n, lmax);
+            const SpecSet st = spec_setting(lam.data(), z.data(), n, alpha, cut, y2);
+            set_out[3 * s] = st.rank;
+            set_out[3 * s + 1] = st.dof;
+            set_out[3 * s + 2] = st.sse;
+            double* beta = coef_out + s * K;
+            for (int j = 0; j < K; ++j) beta[j] = 0.0;
+            for (int i = 0; i < n; ++i) g[i] = spec_g(lam[i], z[i], alpha, cut);
+            for (int c = 0; c < n; ++c) {
+                double acc = 0.0;
+                for (int i = 0; i < n; ++i) acc = fma(g[i], V[(size_t)ord[i] * n + c], acc);
+                beta[live[c]] = acc;
+            }
+        }
+    return FSNAP_OK;
+}

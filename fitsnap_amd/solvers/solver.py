@@ -25,7 +25,8 @@ import numpy as np
 
 from .. import _capi
 from .._hostblas import blas_threads
-from . import ard_path, bcs_path, influence, lasso_path, loco, loco_uq, omp_path, ridge_path, select, select_joint, uq
+from . import (ard_path, bcs_path, influence, lasso_path, loco, loco_uq, omp_path, ridge_path, select, select_joint, spectral_path,
+               uq)
 
 
 class _TrainWeights:
@@ -1304,6 +1305,36 @@ class Solver:
         fit nor the config is changed.  Raises ValueError for other solvers, for ``apply_transpose``, for an empty grid and
         for unknown grid keys."""
         return bcs_path.bcs_path(self, grid, folds, by, fs_dict, b, w, method, table, seed)
+
+    # ------------------------------------------------------------------------------
+    # grouped K-fold spectral paths: ridge alpha x rcond grids (solvers/spectral_path.py, csrc/fsnap_spectral.hip)
+    # ------------------------------------------------------------------------------
+    def spectral_path(self, alphas=None, rconds=None, folds=5, by="Configs", fs_dict=None, b=None, w=None, method="auto",
+                      table="auto", seed=0):
+        """Grouped K-fold cross-validation of the ridge penalty ``alpha`` and of the singular-value cut ``rcond`` over their
+        product grid, after ``perform_fit`` of a RIDGE or SVD solver, from ONE pass over the resident training rows: the units
+        (``fs_dict[by]``, as in ``loco_errors``) are dealt into folds as in ``lasso_path``, the statistics of every (fold, row
+        class) are formed on the GPU, "total minus fold" is eigendecomposed ONCE per fold (Jacobi on the unscaled matrix) and
+        every setting is the filter g_i = z_i / (lambda_i + alpha) on the directions with lambda_i > max(rcond^2, 4 n eps)
+        lambda_max.  Defaults: RIDGE ``alphas = (its alpha,)``, ``rconds = (0,)``; SVD ``alphas = (0,)``, ``rconds =
+        (SVD.RCOND,)``.  An SVD fit that took the row-space path is allowed: the path is about the statistics, and its fits
+        are those of the float64 statistics with the 4 n eps floor, not the row-space fit.  ``method``: "device" (kernels E1
+        and E2 of csrc/fsnap_spectral.hip, K <= 144), "host" (``fsnap_spectral_gram`` over the downloaded fold statistics, any
+        K) or "auto" (the kernels where they exist).  ``table``: "rows" (as in ``lasso_path``, one pass over the rows with the
+        F x Q held-out coefficient vectors; "auto" takes it while F Q <= 512) or "stats" (from the statistics alone: one row
+        per row type and ``*ALL`` with ncount and w_rmse, mae / rmse NaN); both are indexed (alpha, rcond, Row_Type).
+        ``folds``, labels, truths and weights as in ``lasso_path``.  Collective on several ranks; a unit may span ranks.
+
+        Returns ``spectral_path.SpectralPath``: ``alphas``, ``rconds``, ``grid`` (the (alpha, rcond) of setting q = ia Qr +
+        ir), ``fits`` (Q x K, on all training rows), ``rank`` / ``dof`` / ``train_sse`` ((F + 1) x Q, row F the fits on all
+        rows; dof = sum_kept lambda_i / (lambda_i + alpha)), ``gcv`` (n sse / (n - dof)^2 of the fits on all rows),
+        ``eigenvalues`` ((F + 1) x K ascending, zero past the live columns: the spectrum of every refit), ``sweeps`` and
+        ``status`` (per problem; 0 converged, 2 the cap of 60 sweeps reached), ``table``, ``fold_of_unit``, ``cv_error`` /
+        ``cv_se`` (pooled weighted held-out mean squared error per setting and its standard error over the folds), ``best`` /
+        ``best_alpha`` / ``best_rcond`` (the smallest ``cv_error``; ties to the larger alpha, then the larger rcond) and
+        ``simplest`` / ``simplest_alpha`` / ``simplest_rcond`` (the smallest ``dof`` within one ``cv_se`` of the best).
+        Neither the fit nor the config is changed.  Raises ValueError for other solvers and for ``apply_transpose``."""
+        return spectral_path.spectral_path(self, alphas, rconds, folds, by, fs_dict, b, w, method, table, seed)
 
     # ------------------------------------------------------------------------------
     # grouped K-fold greedy sparse-selection paths (solvers/omp_path.py, csrc/fsnap_omp.hip)

@@ -524,6 +524,35 @@ int fsnap_bcs_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const dou
                    int64_t max_active, int deletion, double* coef_out, int32_t* active_out, double* alpha_out,
                    double* errbar_out, int32_t* picks_out, double* info_out, double* heldout_out, double* sig_out);
 
+/* Grouped K-fold spectral paths on per-fold statistics: every ridge penalty alpha and every singular-value cut rcond from ONE
+ * symmetric eigendecomposition per fold (kernel S1 of csrc/fsnap_lasso.hip, E1 and E2 of csrc/fsnap_spectral.hip; the host
+ * route, the picks and the tables are solvers/spectral_path.py).  d_stats (DEVICE), the folds and the total T as for
+ * fsnap_lasso_path.  Problem f < F is the refit without fold f, f = F the fit on all training rows:
+ *     Qm = T.G - G_f,  qv = T.c - c_f,  y2 = T.bb - bb_f                                                (f = F: T alone)
+ * run through fsnap_spectral_gram's scheme (below) with diag_ref = T.G_jj.  Settings are the product grid of alphas[Qa] and
+ * rconds[Qr] (host), q = ia Qr + ir, Q = Qa Qr.  Outputs (host): eig_out[(F + 1)][K] and z_out[(F + 1)][K], ascending, zero
+ * past n_live; info_out[(F + 1)][6] = n_live, sweeps, final off / diag ratio sqrt(sum_{i>j} a_ij^2 / sum_i a_ii^2),
+ * lambda_max, smallest lambda, status (0 converged, 2 the cap of 60 sweeps reached: not an error); set_out[(F + 1)][Q][3] =
+ * rank, dof, sse; fit_out[Q][K], the coefficients of the f = F problems; coef_out[F][Q][K], the coefficients of the refits
+ * (may be NULL: needed only for a row pass); heldout_out[F][Q][nsub][3] = n_{f,s}, bb_{f,s} - 2 beta . c_{f,s} + beta^T G_{f,s}
+ * beta (the weighted squared error of row class s of fold f under the fold's own refit), bb_{f,s}, against block f nsub + s.
+ * FSNAP_E_ARG for K outside 1 ... 144, F < 1, nsub < 1, Qa < 1 or Qr < 1, a negative or non-finite alpha or rcond, a NULL
+ * pointer (coef_out may be NULL), F * nsub blocks or the results past FSNAP_CAT_STATS_MAX_BYTES: nothing is launched then.
+ * FSNAP_NUM_NONFINITE for a NaN/Inf among the fits.  Kernel E1: one workgroup of 1024 threads per problem, the working matrix
+ * as a packed lower triangle in LDS (83.5 KB at K = 144), the eigenvectors in LDS for K <= 113 and in a per-workgroup scratch
+ * that stays in L2 beyond -- the device route serves all of K <= 144.  Kernel E2: one workgroup per (problem, 16 settings).
+ * fp64 VALU, no atomics; every sum runs in an order that depends on the problem and the setting alone: bit-identical run to
+ * run and under any permutation or subset of the grid or of the folds.  Host and kernel run one text (csrc/
+ * fsnap_spectral_body.h) with explicit fmas; the held-out sums of the Python host route are numpy's, in another order.  The
+ * resident rows, weights, mask and category layout are not touched.  Synchronous. */
+int fsnap_spectral_path(fsnap_ctx* ctx, int64_t K, int64_t F, int64_t nsub, const double* d_stats, const double* alphas,
+                        int64_t Qa, const double* rconds, int64_t Qr, double* eig_out, double* z_out, double* info_out,
+                        double* set_out, double* fit_out, double* coef_out, double* heldout_out);
+
+/* ms_out[2] = the times of kernel E1 (eigendecompositions) and kernel E2 (settings) of the context's last successful
+ * fsnap_spectral_path call, between HIP events on its stream.  FSNAP_E_STATE without such a call. */
+int fsnap_spectral_path_times(fsnap_ctx* ctx, double* ms_out);
+
 /* Joint scores of units (normally configurations) of the resident rows for active learning (kernels J1, J2 of
  * csrc/fsnap_joint.hip, fp64 MFMA; the host algebra is solvers/select_joint.py).  With the posterior C = M M^T (M: K x J),
  * the noise variance tau of a unit-weight row, the weighted rows X_u = diag(omega) A_u (n_u x K) of unit u, Z = X_u M and a
@@ -683,6 +712,29 @@ int fsnap_omp_gram(int64_t K, const double* Q, const double* q, double y2, const
 int fsnap_bcs_gram(int64_t K, const double* Q, const double* q, double y2, double sum_y, double n, const double* diag_ref,
                    double sigma2, double scale, double eta, int64_t itermax, int64_t max_active, int deletion, double* coef,
                    int32_t* active, double* alpha, double* mu, double* errbars, double* Sig, int32_t* picks, double* info);
+
+/* Spectral path of ONE system on the statistics: the ridge fits (Q + alpha I) beta = q and the truncated least-squares fits of
+ * lstsq(rcond) for every setting of a grid from one eigendecomposition (the host route of fsnap_spectral_path above and its
+ * check; solvers/spectral_path.py).  Column j is dead -- coefficient 0, no part in the decomposition -- when diag_ref[j] == 0
+ * or Q_jj <= 1e-10 diag_ref[j] (diag_ref = NULL: Q's own diagonal); L are the n_live live columns.
+ * (1) Q[L, L] = V diag(lambda) V^T by two-sided Jacobi rotations on the unscaled matrix (Jacobi resolves the small eigenvalues
+ * of graded matrices to high relative accuracy; alpha and rcond both live in unscaled coordinates): the rotation formula, the
+ * skip of |a_pq| <= 1e-18 sqrt(|a_pp| |a_qq|), the stop at off^2 <= 1e-34 diag^2 and the cap of 60 sweeps are the internal
+ * eigensolver's behind fsnap_solve; the pairs of a sweep come in the round-robin (circle tournament) order of csrc/
+ * fsnap_spectral_body.h, whose rounds hold disjoint pairs and rotate from the matrix before the round.  Reaching the cap is
+ * status 2, not an error.  (2) The eigenpairs are sorted ascending by (lambda, position on the rotated diagonal); every sum
+ * over i below runs in that order, so a setting's result does not depend on the rest of the grid.  lambda_max = max |lambda_i|,
+ * z_i = v_i . q[L].  (3) Setting q = ia Qr + ir = (alpha = alphas[ia] >= 0, rcond = rconds[ir] >= 0): cut = max(rcond^2,
+ * 4 n_live eps) lambda_max (the floor of fsnap_solve's SOLVE_LSTSQ); direction i is kept iff lambda_i > cut; g_i = z_i /
+ * (lambda_i + alpha) when kept, else 0; beta[L] = V g, beta = 0 on dead columns; rank = the kept directions; dof = sum_kept
+ * lambda_i / (lambda_i + alpha); sse = max(y2 - 2 g . z + sum lambda_i g_i^2, 0).  Without a live column: no eigenpairs, rank
+ * 0, beta = 0.  Outputs: eig[K] and z[K] ascending, zero past n_live; info[6] = n_live, sweeps, final off / diag ratio,
+ * lambda_max, smallest lambda, status; set[Qa Qr][3] = rank, dof, sse; coef[Qa Qr][K].  FSNAP_E_ARG for K < 1, Qa < 1, Qr < 1,
+ * a negative or non-finite alpha or rcond or a NULL pointer (diag_ref may be NULL); FSNAP_NUM_NONFINITE for a NaN/Inf in the
+ * statistics.  Host side, no context needed. */
+int fsnap_spectral_gram(int64_t K, const double* Q, const double* q, double y2, const double* diag_ref, const double* alphas,
+                        int64_t Qa, const double* rconds, int64_t Qr, double* eig, double* z, double* info, double* set,
+                        double* coef);
 
 /* Same solve, taking the packed statistics [G | c | ...] from DEVICE memory (the buffer
  * fsnap_normal_eq_async / the all-reduce left in HBM).  Small systems are copied to the host
